@@ -19,8 +19,8 @@ scaling, no data-path collective); `value` is the whole-job Mpoints/s.
          --master-port P bench.py --gpus N --steps K --warmup W     # ... or is started as one of them
 
 The timed region is tmc2rs.sharding.timed_region (the function the world-size-2 gloo test runs): W warm-up
-steps, then K steps between barrier + synchronisation pairs; K is raised to `steps_effective` until the
-region lasts >= --min-seconds (a step is ~0.1 ms).  Every 16th launch of the region carries a HIP-event pair
+steps, then exactly K = --steps steps between barrier + synchronisation pairs (`steps_effective`); --min-seconds S > 0
+raises K until the region lasts >= S (a step is ~0.1 ms).  Every 16th launch of the region carries a HIP-event pair
 on the launch stream (profile mode of the library; a pair on EVERY launch would add ~10 us of stream time per
 step), so `roofline.kernel_ms` is the mean duration of launches `ms_per_step` was measured on.
 
@@ -48,6 +48,10 @@ One JSON line is printed by rank 0, with the contract fields plus
                     Decoder at the end of the run.
   cpu_baseline    : the CPU oracle (a port of the reference's algorithm; the Rust crate cannot be built
                     here) timed single-threaded on this box, rank 0 at N=1 only.
+
+--dump-outputs DIR (rank 0) writes, right after the timed region, what the last timed step computed for every entry of
+its batch, as float32 / float64 .npy files (under 64 MB in all; see dump_outputs).  The inputs depend only on the
+arguments, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -92,8 +96,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--min-seconds", type=float, default=0.5,
-                    help="the timed region runs max(--steps, enough steps to last this long)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="if > 0, the timed region runs max(--steps, enough steps to last this long); "
+                         "by default it runs exactly --steps steps")
     ap.add_argument("--ramp-ms", type=float, default=150.0,
                     help="untimed launches before the warmup steps until this much wall time has passed: a step is ~0.1 ms, "
                          "far shorter than the GPU's clock ramp from idle")
@@ -130,6 +135,9 @@ def parse():
                     help="an event pair around every n-th launch of the timed region (each costs a few us of stream time)")
     ap.add_argument("--profile-steps", type=int, default=0, help=argparse.SUPPRESS)   # accepted for old tool scripts
     ap.add_argument("--no-fresh-gof", action="store_true", help="skip the `fresh_gof` leg (create + reconstruct + destroy per step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (point counts, CRCs and a seeded sample of the points of "
+                         "every batch entry) to DIR/<name>.npy (rank 0)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: the launch of the ranks, the process group (VPCC_BENCH_BACKEND, default gloo here), the timed "
                          "region's barriers and its MAX / SUM / MIN reductions with a step that only sleeps — what `--gpus N` "
@@ -200,6 +208,41 @@ def end_to_end_leg(frames, args, device):
         if os.path.exists(path):
             os.remove(path)
         os.rmdir(d)
+
+
+DUMP_BUDGET_BYTES = 60 << 20       # stays under 64 MB with the per-entry arrays
+
+
+def dump_outputs(g, n_batch, path, max_sample=8192):
+    """What a caller of the timed path receives from `g` (vpcc_gof_download of every batch entry), as .npy files:
+      point_counts [n_batch]          float64  points of each entry
+      xyz_crc32, rgb_crc32 [n_batch]  float64  CRC32 of each entry's whole xyz (u16 x3) / rgb (u8 x3) array
+      sample_index [n_batch, S]       float32  sorted point indices drawn with a seed fixed per entry; -1 past the count
+      xyz [n_batch, S, 3]             float32  those points' coordinates (-1 where sample_index is -1)
+      rgb [n_batch, S, 3]             float32  those points' colours (-1 where sample_index is -1)
+    S = max_sample, lowered so that the files stay within DUMP_BUDGET_BYTES."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    S = max(1, min(max_sample, (DUMP_BUDGET_BYTES - 24 * n_batch) // (28 * n_batch)))
+    counts = np.zeros(n_batch, np.float64)
+    crc = np.zeros((2, n_batch), np.float64)
+    index = np.full((n_batch, S), -1, np.float32)
+    xyz = np.full((n_batch, S, 3), -1, np.float32)
+    rgb = np.full((n_batch, S, 3), -1, np.float32)
+    for i in range(n_batch):
+        res = g.download(i)
+        n = int(res["n"])
+        counts[i] = n
+        crc[0, i] = zlib.crc32(np.ascontiguousarray(res["xyz"]).tobytes())
+        crc[1, i] = zlib.crc32(np.ascontiguousarray(res["rgb"]).tobytes())
+        k = min(n, S)
+        idx = np.sort(np.random.default_rng([0x5EED, i]).choice(n, size=k, replace=False)) if k else np.zeros(0, np.int64)
+        index[i, :k] = idx
+        xyz[i, :k] = res["xyz"][idx]
+        rgb[i, :k] = res["rgb"][idx]
+    for name, a in (("point_counts", counts), ("xyz_crc32", crc[0]), ("rgb_crc32", crc[1]),
+                    ("sample_index", index), ("xyz", xyz), ("rgb", rgb)):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def launch_ranks(n):
@@ -366,6 +409,8 @@ def main():
     ev[1].record(ext)
     ev[1].synchronize()
     steps_eff = reg["steps_effective"]
+    if args.dump_outputs and rank == 0:                              # outside the timed region
+        dump_outputs(gofs[(turn[0] - 1) % len(gofs)], n_batch, args.dump_outputs)
     elapsed = reg["elapsed_s"]
     region_ms_per_step = ev[0].elapsed_time(ev[1]) / steps_eff
     # the timed region's own launches: every --profile-every-th of them carries an event pair
