@@ -288,14 +288,20 @@ void vpcc_gof_destroy(vpcc_gof* gof);
  * (a hipStream_t passed as void*; NULL = the context's own stream).  Returns
  * immediately; results are valid after vpcc_gof_sync() or a stream sync.
  * Launches on one gof are serialised by the library (a launch on a different stream first waits for the
- * previous launch's kernels): they share the gof's output arrays and control words.  A device-side error
- * (VPCC_ERR_DEVICE from the counts/download calls: a look-back wait that gave up) is sticky for the gof.
+ * previous launch's kernels): they share the gof's output arrays and control words.
+ * Every frame of [first, first+count) gets the results of THIS launch — its points, and its point count even when that
+ * is 0 (an all-zero occupancy plane).  A frame outside the range keeps its points, its point count and its status of
+ * the last launch that covered it (a frame never covered: 0 points), even when its borrowed planes have changed since;
+ * only vpcc_gof_block_to_patch looks at a frame's planes outside a launch.
+ * VPCC_ERR_CAPACITY is not sticky: it describes the frame's last launch.  Device-side errors are sticky for the gof —
+ * no later launch clears them: VPCC_ERR_DEVICE from the counts/download calls (a look-back wait that gave up) and
+ * VPCC_ERR_UNSUPPORTED (a smoothing cell beyond its bound, vpcc_gof_smooth).
  * Every vpcc_* call that touches the GPU makes the context's device the calling thread's current HIP
  * device and leaves it so (vpcc_host_free does not). */
 int vpcc_gof_reconstruct(vpcc_gof* gof, uint32_t first, uint32_t count, void* hip_stream);
 int vpcc_gof_sync(vpcc_gof* gof);
 
-/* Per-frame point counts of the last reconstruct (synchronises). */
+/* Per-frame point counts of the last reconstruct that covered each frame (synchronises). */
 int vpcc_gof_point_counts(vpcc_gof* gof, uint32_t* counts_out /* n_frames */);
 
 /* block_to_patch of frame `frame` (src/codec.rs:205-250: 0 = unowned, else patch index + 1; (width / R) x (height / R)

@@ -604,6 +604,18 @@ def test_borrowed_planes_may_change_between_launches(ctx):
     b2p, items = g.block_to_patch(0, (a["width"] // 16) * (a["height"] // 16))
     assert np.array_equal(b2p.astype(np.uint64), ref_mixed["block_to_patch"].astype(np.uint64))
     assert items == int(np.count_nonzero(ref_mixed["block_to_patch"]))
+    # a third launch over an all-zero occupancy plane: no work items and no points — not the count of the launch before
+    with torch.cuda.stream(stream):
+        slots[0].zero_()                                                    # (slots[0]: the occupancy plane)
+        g.reconstruct(stream=stream.cuda_stream)
+    empty = dict(mixed)
+    empty["occupancy"] = np.zeros_like(b["occupancy"])
+    ref_empty = ob.reconstruct(empty)[1]
+    assert ref_empty["n"] == 0
+    assert g.point_counts()[0] == 0
+    _check(g.download(0), ref_empty)
+    b2p, items = g.block_to_patch(0, (a["width"] // 16) * (a["height"] // 16))
+    assert items == 0 and not b2p.any()
     g.close()
 
 

@@ -313,6 +313,15 @@ def test_smoothing_cell_bound_is_checked():
     with pytest.raises(recon.VpccError) as e:
         g.download(0)
     assert e.value.status == _abi.VPCC_ERR_UNSUPPORTED and "one grid cell" in str(e.value)
+    # sticky (vpcc_gof_smooth): a later launch of the gof does not clear it, whatever that launch produces
+    g.reconstruct()
+    with pytest.raises(recon.VpccError) as e:
+        g.download(0)
+    assert e.value.status == _abi.VPCC_ERR_UNSUPPORTED
+    with pytest.raises(recon.VpccError) as e:
+        g.point_counts()
+    assert e.value.status == _abi.VPCC_ERR_UNSUPPORTED
+    assert g.frame_status(0) == _abi.VPCC_ERR_UNSUPPORTED
     g.close()
     ctx.close()
 

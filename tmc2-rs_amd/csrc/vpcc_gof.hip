@@ -112,7 +112,8 @@ extern "C" int vpcc_gof_reconstruct(vpcc_gof* g, uint32_t first, uint32_t count,
     }
     // Nothing to clear: look-back words and ticket counters carry the launch generation (a counter of an earlier
     // launch is reset by the first workgroup that draws from it), and a frame's point count is rewritten by its last group
-    // (a frame without tiles keeps the zero written at creation).
+    // — or, for a frame whose occupancy leaves it no tiles in THIS launch, by the planning kernel (an earlier launch may
+    // have left a count there).
     if (!g->tile_map_valid || g->tile_map_first != first || g->tile_map_count != count) {
       std::vector<uint32_t> tiles(count);
       for (uint32_t i = 0; i < count; ++i) tiles[i] = g->shapes[first + i].tile_bound;   // (the exact counts are on the device: the planning kernel's)
@@ -217,7 +218,8 @@ extern "C" int vpcc_gof_block_to_patch(vpcc_gof* g, uint32_t frame, uint32_t* bl
   const size_t n = (size_t)g->shapes[frame].bw * g->shapes[frame].bh;
   if (!g->general && g->plan_in_lds) {
     // a launch keeps block_to_patch in the planning kernel's LDS (the tile kernel works from the items): planned once more
-    // for this frame, from the planes as they are now, with the map written out (the items it rewrites are the same)
+    // for this frame, from the planes as they are now, with the map written out (the items it rewrites are planned again by
+    // the next launch; the point count is left alone: it is the last launch's)
     launch_plan_tiles(g->d_frames, frame, 1, plan_tiles_lds_launch_bytes((uint32_t)n, g->shapes[frame].n_patches), true, s);
     HIP_TRY(ctx, hipGetLastError());
   }

@@ -332,7 +332,12 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_tiles(DevFrame* frames_rw
     }
   }
   VPCC_STAMP(7);
-  if (tid == 0) *glw(&frames_rw[first + blockIdx.x].n_tiles) = base_items;
+  if (tid == 0) {
+    *glw(&frames_rw[first + blockIdx.x].n_tiles) = base_items;
+    // no tiles: no group of k_recon_tiles writes the frame's point count, so the launch does (a query — write_b2p — must
+    // leave the count of the last launch alone)
+    if (!write_b2p && base_items == 0u) *glw(f.n_points) = 0u;
+  }
   // block_to_patch leaves the LDS for whoever asked (vpcc_gof_block_to_patch plans once more for it)
   if (write_b2p) {
     VPCC_GLOBAL uint32_t* const out_b2p = glw(f.block_to_patch);
@@ -404,7 +409,10 @@ __global__ __launch_bounds__(1024) void k_plan_items(DevFrame* __restrict__ fram
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) f.n_tiles = base_s;
+  if (threadIdx.x == 0) {
+    f.n_tiles = base_s;
+    if (base_s == 0u) *f.n_points = 0u;                                   // (no group of k_recon_tiles will write it)
+  }
 }
 void launch_plan_tiles(DevFrame* d_frames, uint32_t first, uint32_t count, size_t lds_bytes, bool write_block_to_patch, void* stream) {
   if (!count) return;
