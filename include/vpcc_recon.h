@@ -391,6 +391,39 @@ typedef struct vpcc_smoothing_params {
 int vpcc_gof_smooth(vpcc_gof* gof, uint32_t first, uint32_t count, const vpcc_smoothing_params* params,
                     void* hip_stream);
 
+/* ---------------------------------------------------------------- frame digests */
+/* A 64-bit digest of a reconstructed frame and of a frame's input planes, computed on the GPU (k_digest_outputs,
+ * k_digest_planes) and on the host by the same definition.  It is a CHECKSUM for detecting errors — a wrong byte, a lost or
+ * reordered point — not a cryptographic hash: anyone can construct a different frame with the same digest.
+ *
+ * Arithmetic is on uint64 and wraps.  G = 0x9E3779B97F4A7C15.
+ *
+ *   mix64(z):  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   digest(head, rows) = mix64(head ^ G) + Σ over rows (p, y, bytes) Σ_k mix64(q_k ^ (((p << 56) | (y << 32) | k) * G))
+ *       q_k = bytes [8k, 8k+8) of the row, zero-padded at its end to a multiple of 8, read little-endian
+ *
+ * Output digest of a frame with n points: head = n; rows (0, 0, the 6n bytes of xyz), then (1, 0, the 3n bytes of rgb)
+ * when the frame has colours.  The patch-index output is not included.
+ * Plane digest of a frame: head = (width << 32) | height; only the logical elements of each plane, never stride padding;
+ * u16 values little endian.  p = 0: the occupancy rows, y < occ_h, each occ_w bytes; p = 1 + m: geometry luma of map m,
+ * `height` rows of 2·width bytes; p = 3 + 3m + c, for c = Y, U, V: attribute planes of map m when attribute_count is
+ * non-zero — Y is width × height, U and V are (width/2) × (height/2).
+ *
+ * mix64 is a bijection, so changing any single 8-byte word always changes the digest; the sum commutes, so the order of a
+ * GPU reduction cannot change it; the position (p, y, k) enters every term, so reordered points change it except with
+ * probability about 2^-64. */
+int vpcc_digest_points(const vpcc_point3* xyz, const vpcc_color3* rgb /* may be NULL */, size_t n, uint64_t* out);
+/* Host plane pointers. */
+int vpcc_digest_frame_planes(const vpcc_frame_desc* frame, uint64_t* out);
+/* Output digests of frames [first, first+count) as they are on the device: stream-ordered behind everything enqueued on the
+ * gof (reconstruct, smooth); waits for the result.  VPCC_ERR_STATE before the first launch.  A frame whose last launch
+ * produced more points than the gof's capacity (VPCC_ERR_CAPACITY) is hashed with head = its point count and rows cut at
+ * the capacity. */
+int vpcc_gof_output_digests(vpcc_gof* gof, uint32_t first, uint32_t count, uint64_t* out /* count */);
+/* Plane digests of frames [first, first+count) over the gof's device planes — its own copies or the borrowed ones, as they
+ * are when the kernel runs (behind the gof's ingest and launches); waits for the result. */
+int vpcc_gof_plane_digests(vpcc_gof* gof, uint32_t first, uint32_t count, uint64_t* out /* count */);
+
 /* ------------------------------------------------- host mirror of the library API */
 /* C view of the C++ class tmc2rs::Decoder (tmc2-rs_amd/csrc/decoder.hpp), which mirrors the
  * reference's public API: Decoder::new (src/lib.rs:71-78), start() (:97-138), recv_frame() (:143-145).
@@ -443,6 +476,37 @@ typedef struct vpcc_decoder_stats_t {
   int32_t numa_node[8];            /* NUMA node lane i was bound to (-1: none reported), first 8 lanes */
 } vpcc_decoder_stats_t;
 int  vpcc_decoder_stats(const vpcc_decoder* dec, vpcc_decoder_stats_t* out);
+/* Verified mode (opt-in; off: nothing of the path changes).  Between open and start; without the call the environment
+ * variable VPCC_DECODER_VERIFY=ingest,reconstruct,delivery (any of them, comma separated) or =all decides.  A frame is
+ * handed over only after the checks asked for pass:
+ *   INGEST       the device plane digest of the frame equals the host plane digest of its source in the input buffer
+ *                (every ingest route: extent copies, pull kernel, per-plane copies, plain uploads);
+ *   RECONSTRUCT  the frame is reconstructed a second time, into outputs of its own, by the general sequence's per-pixel pass
+ *                (k_general) of a second gof that borrows the first one's device planes, and both output digests (before
+ *                smoothing) agree.  The check never runs the kernel that made the delivered output — except for frames
+ *                the primary itself sent through k_general (VPCC_GENERAL_ANY_FRAME), where it is the same kernel run twice;
+ *   DELIVERY     the digest of the host arrays handed to the consumer equals the device output digest after smoothing.
+ * On a mismatch the stream stops as on a device error: earlier frames have been delivered, that frame and every later one
+ * are not, vpcc_decoder_recv_frame returns 0 and vpcc_decoder_error reads
+ * "verify: <stage> mismatch at frame <index in the stream> (expected 0x..., got 0x...)".
+ * Host hashing runs on the lanes and on a verify pool of at most 8 threads, never on the consumer's thread. */
+#define VPCC_VERIFY_INGEST      0x1u
+#define VPCC_VERIFY_RECONSTRUCT 0x2u
+#define VPCC_VERIFY_DELIVERY    0x4u
+#define VPCC_VERIFY_ALL         0x7u
+int  vpcc_decoder_set_verify(vpcc_decoder* dec, uint32_t flags);
+/* Output digest of the last received frame: needs VPCC_VERIFY_DELIVERY (else VPCC_ERR_STATE, also before a frame). */
+int  vpcc_decoder_frame_digest(vpcc_decoder* dec, uint64_t* out);
+typedef struct vpcc_decoder_verify_stats_t {
+  uint32_t flags;                  /* VPCC_VERIFY_* in force */
+  uint32_t reserved;
+  uint64_t ingest_frames;          /* frames that passed each check */
+  uint64_t reconstruct_frames;
+  uint64_t delivery_frames;
+  double host_seconds;             /* host hashing, summed over the threads that did it */
+  double kernel_seconds;           /* HIP-event time of the check kernels (digests, the second reconstruction) */
+} vpcc_decoder_verify_stats_t;
+int  vpcc_decoder_verify_stats(const vpcc_decoder* dec, vpcc_decoder_verify_stats_t* out);
 void vpcc_decoder_close(vpcc_decoder* dec);
 
 /* writer::PlyWriter::write, ASCII (src/writer.rs:25-74); rgb may be NULL (no colour properties). */

@@ -2,7 +2,9 @@
 // reconstruction on one or several MI355X through the C ABI (include/vpcc_recon.h).
 #include "decoder.hpp"
 #include "v3c_syntax.hpp"
+#include "vpcc_digest.hpp"
 
+#include <atomic>
 #include <cctype>
 #include <chrono>
 #include <cstdio>
@@ -205,6 +207,78 @@ class Lane {
   std::thread th_;                                   // last member: starts when everything above exists
 };
 
+// Verified mode: host hashing — of a unit's input planes, of the arrays handed to the consumer — on a few threads of the
+// decoder's own, never on the consumer's.  At most 8 (VPCC_DECODER_VERIFY_THREADS asks for fewer): a command on the GPU machines
+// has 16 CPUs whatever the machine has, and the lanes and the worker need theirs.
+class VerifyPool {
+ public:
+  explicit VerifyPool(size_t n) {
+    for (size_t i = 0; i < n; ++i) th_.emplace_back([this] { run(); });
+  }
+  ~VerifyPool() {
+    {
+      std::lock_guard<std::mutex> lk(m_);
+      stop_ = true;
+      q_.clear();                                      // (nobody waits for what has not started: the stream ended early)
+    }
+    cv_.notify_all();
+    for (auto& t : th_) t.join();
+  }
+  std::future<uint64_t> submit(std::function<uint64_t()> f) {
+    std::packaged_task<uint64_t()> t([this, f = std::move(f)] {
+      const auto t0 = std::chrono::steady_clock::now();
+      const uint64_t v = f();
+      ns_ += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+      return v;
+    });
+    std::future<uint64_t> r = t.get_future();
+    {
+      std::lock_guard<std::mutex> lk(m_);
+      q_.push_back(std::move(t));
+    }
+    cv_.notify_one();
+    return r;
+  }
+  double seconds() const { return (double)ns_.load() * 1e-9; }
+
+ private:
+  void run() {
+    for (;;) {
+      std::packaged_task<uint64_t()> t;
+      {
+        std::unique_lock<std::mutex> lk(m_);
+        cv_.wait(lk, [&] { return stop_ || !q_.empty(); });
+        if (stop_) return;
+        t = std::move(q_.front());
+        q_.pop_front();
+      }
+      t();
+    }
+  }
+  std::mutex m_;
+  std::condition_variable cv_;
+  std::deque<std::packaged_task<uint64_t()>> q_;
+  std::atomic<uint64_t> ns_{0};
+  bool stop_ = false;
+  std::vector<std::thread> th_;
+};
+
+// "ingest,reconstruct,delivery" (any of them, ',' or '|' between) or "all" -> VPCC_VERIFY_* bits; false on an unknown word.
+bool parse_verify(const char* e, uint32_t* flags) {
+  *flags = 0;
+  std::string w;
+  for (const char* c = e;; ++c) {
+    if (*c && *c != ',' && *c != '|') { if (!std::isspace((unsigned char)*c)) w += *c; continue; }
+    if (w == "ingest") *flags |= VPCC_VERIFY_INGEST;
+    else if (w == "reconstruct") *flags |= VPCC_VERIFY_RECONSTRUCT;
+    else if (w == "delivery") *flags |= VPCC_VERIFY_DELIVERY;
+    else if (w == "all") *flags |= VPCC_VERIFY_ALL;
+    else if (!w.empty()) return false;
+    w.clear();
+    if (!*c) return true;
+  }
+}
+
 // The lanes of a Decoder.  They are made at the very beginning of start(): a lane's first act is vpcc_ctx_create, and the
 // first HIP call of a process initialises the runtime — 0.19-0.24 s on this pool of machines (profiles/r05/cold_start.txt)
 // that now pass while start() reads the input on the caller's thread (src/lib.rs:98), instead of in front of the first frame.
@@ -215,6 +289,19 @@ struct Decoder::LaneSet {
 void Decoder::start() {
   if (started_) throw std::logic_error("library decoder can only be started once");   // src/lib.rs:108-111
   started_ = true;
+  if (params_.verify_from_env) {
+    const char* e = std::getenv("VPCC_DECODER_VERIFY");
+    if (e && !parse_verify(e, &params_.verify)) throw std::runtime_error(std::string("VPCC_DECODER_VERIFY: unknown stage in \"") + e + "\"");
+  }
+  params_.verify &= VPCC_VERIFY_ALL;
+  vstats_.flags = params_.verify;
+  if (const char* e = std::getenv("VPCC_DECODER_TEST_CORRUPT")) {       // tests only: <stage>:<frame>
+    const char* colon = std::strchr(e, ':');
+    const std::string stage = colon ? std::string(e, (size_t)(colon - e)) : std::string();
+    corrupt_stage_ = stage == "ingest" ? 1 : stage == "reconstruct" ? 2 : stage == "delivery" ? 3 : 0;
+    if (!corrupt_stage_) throw std::runtime_error(std::string("VPCC_DECODER_TEST_CORRUPT: expected <ingest|reconstruct|delivery>:<frame>, got \"") + e + "\"");
+    corrupt_frame_ = std::strtoull(colon + 1, nullptr, 10);
+  }
   lanes_ = std::make_shared<LaneSet>();
   {
     const size_t G = params_.devices.empty() ? 1 : params_.devices.size();
@@ -396,17 +483,30 @@ void Decoder::worker() {
     if (!pinned) rest = nullptr;
   }
   step(rest ? "head of the input page-locked" : "input page-locked");
+  // Verified mode (vpcc_decoder_set_verify): device digests travel back with the point counts; host hashing runs on `vpool`.
+  const uint32_t V = params_.verify;
+  std::unique_ptr<VerifyPool> vpool;
+  if (V & (VPCC_VERIFY_INGEST | VPCC_VERIFY_DELIVERY)) {
+    size_t nt = 8;
+    if (const char* e = std::getenv("VPCC_DECODER_VERIFY_THREADS")) nt = std::max<size_t>(1, std::min<size_t>(8, std::strtoull(e, nullptr, 10)));
+    vpool = std::make_unique<VerifyPool>(nt);
+  }
   struct Part {                                       // one device's share of one unit
     std::vector<vpcc_frame_desc> frames;
     vpcc_gof* g = nullptr;
+    vpcc_gof* check = nullptr;                        // VPCC_VERIFY_RECONSTRUCT: the second reconstruction, on g's device planes
+    uint32_t corrupt_local = ~0u;                     // VPCC_DECODER_TEST_CORRUPT (ingest, reconstruct): this part's frame
+    std::vector<uint64_t> dig, check_dig;             // verified mode: the gofs' digest slots (vpcc::DigestSlot x frames)
     std::string err;
     std::future<int> launched;
-    double launch_seconds = 0, kernel_seconds = 0;
+    double launch_seconds = 0, kernel_seconds = 0, verify_kernel_seconds = 0;
   };
   struct InFlight {
     std::vector<const vpcc_frame_desc*> frames;       // the unit's frames in presentation order
     std::vector<Part> part;
     vpcc_smoothing_params smooth{};                   // flags != 0: the unit's frames are smoothed behind their reconstruction
+    uint64_t first_index = 0;                         // index in the stream of the unit's first frame
+    std::vector<std::future<uint64_t>> host_planes;   // VPCC_VERIFY_INGEST: plane digests of the frames' sources (verify pool)
   };
   // What the post-processing switches make of a GOF (src/decoder.rs:291-299): geometry smoothing needs the switch AND the
   // SEI (or, for inputs without syntax, the parameters given in Params); colour smoothing its switch and an attribute.
@@ -447,16 +547,37 @@ void Decoder::worker() {
     f->part.clear();
     f->part.resize(G);
     for (size_t i = 0; i < f->frames.size(); ++i) f->part[i % G].frames.push_back(*f->frames[i]);
+    const int cs = corrupt_stage_;
+    if ((cs == 1 || cs == 2) && corrupt_frame_ >= f->first_index && corrupt_frame_ - f->first_index < f->frames.size()) {
+      const size_t i = (size_t)(corrupt_frame_ - f->first_index);
+      f->part[i % G].corrupt_local = (uint32_t)(i / G);
+    }
     for (size_t d = 0; d < G; ++d) {
       Part* p = &f->part[d];
       if (p->frames.empty()) continue;
       const vpcc_smoothing_params sp = f->smooth;
-      p->launched = lanes[d]->post([p, pinned, now, secs, sp](vpcc_ctx* c) {
+      p->launched = lanes[d]->post([p, pinned, now, secs, sp, V, cs](vpcc_ctx* c) {
         const auto t0 = now();
-        int st = vpcc_gof_create(c, p->frames.data(), (uint32_t)p->frames.size(), VPCC_MEM_HOST, 0,
+        const uint32_t n = (uint32_t)p->frames.size();
+        int st = vpcc_gof_create(c, p->frames.data(), n, VPCC_MEM_HOST, 0,
                                  (pinned ? VPCC_GOF_ASYNC_UPLOAD : 0u) | VPCC_GOF_PROFILE | (sp.flags ? VPCC_GOF_WANT_PATCH_INDEX : 0u), &p->g);
-        if (st == VPCC_OK) st = vpcc_gof_reconstruct(p->g, 0, (uint32_t)p->frames.size(), nullptr);   // ONE launch, asynchronous
-        if (st == VPCC_OK && sp.flags) st = vpcc_gof_smooth(p->g, 0, (uint32_t)p->frames.size(), &sp, nullptr);   // src/decoder.rs:291-299
+        if (st == VPCC_OK && cs == 1 && p->corrupt_local != ~0u) st = vpcc::gof_test_flip_byte(p->g, p->corrupt_local, 0);
+        if (st == VPCC_OK && (V & VPCC_VERIFY_INGEST)) st = vpcc::gof_enqueue_plane_digests(p->g, 0, n, vpcc::kSlotPlanes);
+        if (st == VPCC_OK) st = vpcc_gof_reconstruct(p->g, 0, n, nullptr);   // ONE launch, asynchronous
+        if (st == VPCC_OK && cs == 2 && p->corrupt_local != ~0u) st = vpcc::gof_test_flip_byte(p->g, p->corrupt_local, 1);
+        if (st == VPCC_OK && (V & VPCC_VERIFY_RECONSTRUCT)) {
+          // the primary's digest before smoothing, and a second reconstruction of the same device planes by k_general into outputs
+          // of its own (a gof that borrows them: on the same stream, behind the primary's ingest)
+          st = vpcc::gof_enqueue_output_digests(p->g, 0, n, vpcc::kSlotOutputs);
+          std::vector<vpcc_frame_desc> dev(p->frames);
+          for (uint32_t i = 0; i < n && st == VPCC_OK; ++i) st = vpcc::gof_device_plane_desc(p->g, i, &dev[i]);
+          if (st == VPCC_OK)
+            st = vpcc::gof_create_check(c, dev.data(), n, &p->check);
+          if (st == VPCC_OK) st = vpcc_gof_reconstruct(p->check, 0, n, nullptr);
+          if (st == VPCC_OK) st = vpcc::gof_enqueue_output_digests(p->check, 0, n, vpcc::kSlotOutputs);
+        }
+        if (st == VPCC_OK && sp.flags) st = vpcc_gof_smooth(p->g, 0, n, &sp, nullptr);   // src/decoder.rs:291-299
+        if (st == VPCC_OK && (V & VPCC_VERIFY_DELIVERY)) st = vpcc::gof_enqueue_output_digests(p->g, 0, n, vpcc::kSlotOutputsSmoothed);
         if (st) p->err = std::string(vpcc_status_string(st)) + ": " + vpcc_last_error(c);
         p->launch_seconds = secs(t0, now());
         return st;
@@ -468,7 +589,13 @@ void Decoder::worker() {
       if (f->part[d].launched.valid() || f->part[d].g) {
         Part* p = &f->part[d];
         if (p->launched.valid()) p->launched.wait();
-        lanes[d]->post([p](vpcc_ctx*) { vpcc_gof_destroy(p->g); p->g = nullptr; return 0; }).get();
+        lanes[d]->post([p](vpcc_ctx*) {
+          vpcc_gof_destroy(p->check);                  // (it borrows g's planes: it goes first)
+          p->check = nullptr;
+          vpcc_gof_destroy(p->g);
+          p->g = nullptr;
+          return 0;
+        }).get();
       }
   };
 
@@ -500,7 +627,8 @@ void Decoder::worker() {
     auto gof_bytes = [&](const DecodedGof& g) {
       uint64_t b = 0;
       for (const vpcc_frame_desc& fr : g.frames)
-        b += (uint64_t)fr.map_count * fr.width * fr.height * (4 + 9 + (fr.attribute_count ? 3 : 0));   // planes + output capacity bound
+        b += (uint64_t)fr.map_count * fr.width * fr.height * (4 + 9 + (fr.attribute_count ? 3 : 0) +   // planes + output capacity bound
+                                                               ((V & VPCC_VERIFY_RECONSTRUCT) ? 6 + (fr.attribute_count ? 3 : 0) : 0));   // + the check's outputs
       return b;
     };
     bytes = gof_bytes(gofs_[k]);
@@ -538,6 +666,7 @@ void Decoder::worker() {
     ~Cleanup() { for (auto& f : q) destroy_fn(&f); }
   } cleanup{inflight, destroy};
   size_t launched = 0;
+  uint64_t next_index = 0;                            // index in the stream of the next unit's first frame
   // Units are posted up to kAhead ahead (their ingest overlaps the current unit's work) — but only once the current
   // unit's point counts are back and its first downloads are posted: a lane serves its queue in order, and with the
   // look-ahead posted first the first unit's counts and downloads waited behind the planning and allocation of the next
@@ -549,7 +678,12 @@ void Decoder::worker() {
       inflight.back().smooth = smoothing_of(gofs_[units[launched].first]);
       for (size_t q = units[launched].first; q < units[launched].second; ++q)
         for (const vpcc_frame_desc& fr : gofs_[q].frames) inflight.back().frames.push_back(&fr);
+      inflight.back().first_index = next_index;
+      next_index += inflight.back().frames.size();
       launch(&inflight.back());
+      if (V & VPCC_VERIFY_INGEST)                       // the sources' plane digests, while the unit travels
+        for (const vpcc_frame_desc* fr : inflight.back().frames)
+          inflight.back().host_planes.push_back(vpool->submit([fr] { return vpcc::digest_frame_planes(*fr); }));
       ++launched;
     }
   };
@@ -591,13 +725,29 @@ void Decoder::worker() {
         Part* p = &cur.part[d];
         uint32_t* out = counts[d].data();
         std::string* e = &errs[d];
-        fc[d] = lanes[d]->post([p, out, e](vpcc_ctx* c) {
+        fc[d] = lanes[d]->post([p, out, e, V](vpcc_ctx* c) {
           int st = vpcc_gof_point_counts(p->g, out);            // waits for the launch
           if (st) *e = vpcc_last_error(c);
           const char* names[8];
           float ms[8];
           const int nk = st ? 0 : vpcc_gof_kernel_times(p->g, names, ms, 8);
           for (int q = 0; q < nk; ++q) p->kernel_seconds += ms[q] * 1e-3;
+          if (!st && V) {                                        // the device digests come back with the counts
+            double ks = 0;
+            p->dig.assign((size_t)vpcc::kDigestSlots * p->frames.size(), 0);
+            st = vpcc::gof_read_digests(p->g, p->dig.data(), &ks);
+            p->verify_kernel_seconds += ks;
+            if (!st && p->check) {
+              std::vector<uint32_t> cc(p->frames.size());
+              st = vpcc_gof_point_counts(p->check, cc.data());   // (its sticky device errors)
+              p->check_dig.assign((size_t)vpcc::kDigestSlots * p->frames.size(), 0);
+              if (!st) st = vpcc::gof_read_digests(p->check, p->check_dig.data(), &ks);
+              p->verify_kernel_seconds += ks;
+              const int nc = st ? 0 : vpcc_gof_kernel_times(p->check, names, ms, 8);
+              for (int q = 0; q < nc; ++q) p->verify_kernel_seconds += ms[q] * 1e-3;
+            }
+            if (st) *e = std::string("verify: ") + vpcc_last_error(c);
+          }
           return st;
         });
       }
@@ -606,7 +756,10 @@ void Decoder::worker() {
       for (size_t d = 0; d < G; ++d)
         if (fc[d].valid() && fc[d].get() && bad < 0) bad = (int)d;
       if (bad >= 0) { fail(errs[(size_t)bad]); return; }
-      for (size_t d = 0; d < G; ++d) stats_.kernel_seconds += cur.part[d].kernel_seconds;
+      for (size_t d = 0; d < G; ++d) {
+        stats_.kernel_seconds += cur.part[d].kernel_seconds;
+        vstats_.kernel_seconds += cur.part[d].verify_kernel_seconds;
+      }
       t_counts += secs(t0, now());
       if (k == 0) step("first unit reconstructed (point counts back)");
       if (trace_steps && k) { char b[64]; std::snprintf(b, sizeof b, "unit %zu (%zu frames): point counts back", k, n); step(b); }
@@ -618,8 +771,17 @@ void Decoder::worker() {
     // memory costs milliseconds).
     const size_t window = std::max<size_t>(8, 4 * G);
     std::vector<PointSet3> sets(n);
-    std::vector<std::future<int>> done(n);
+    std::vector<std::shared_future<int>> done(n);
     std::vector<std::string> derr(n);
+    // VPCC_VERIFY_DELIVERY: the digest of each frame's host arrays, on the verify pool once its download is complete.  The jobs
+    // write into `sets`: every one has finished before it goes (declared after it, so destroyed first).
+    std::vector<std::future<uint64_t>> delivered(n);
+    struct WaitDelivered {
+      std::vector<std::future<uint64_t>>& h;
+      ~WaitDelivered() { for (auto& x : h) if (x.valid()) x.wait(); }
+    } wait_delivered{delivered};
+    const bool flip_delivery = corrupt_stage_ == 3 && corrupt_frame_ >= cur.first_index && corrupt_frame_ - cur.first_index < n;
+    const size_t flip_f = flip_delivery ? (size_t)(corrupt_frame_ - cur.first_index) : n;
     size_t posted = 0;
     auto post_downloads = [&](size_t upto) {
       for (; posted < n && posted < upto; ++posted) {
@@ -643,7 +805,19 @@ void Decoder::worker() {
                                                  nullptr, np ? np : 1, &got);
           if (st || got != np) { *e = st ? vpcc_last_error(c) : "point count changed between calls"; return st ? st : (int)VPCC_ERR_DEVICE; }
           return 0;
-        });
+        }).share();
+        if (V & VPCC_VERIFY_DELIVERY) {
+          vpcc_gof* g = p->g;
+          const bool flip = f == flip_f;
+          std::shared_future<int> dl = done[f];
+          delivered[f] = vpool->submit([dl, g, local, ps, flip]() -> uint64_t {
+            if (dl.get() != VPCC_OK || vpcc_gof_download_wait(g, (uint32_t)local) != VPCC_OK) return 0;   // (the worker sees the failure)
+            if (flip && ps->len()) reinterpret_cast<unsigned char*>(ps->positions.data())[0] ^= 1u;           // tests only
+            uint64_t h = 0;
+            (void)vpcc_digest_points(ps->positions.data(), ps->with_colors ? ps->colors.data() : nullptr, ps->len(), &h);
+            return h;
+          });
+        }
       }
     };
     auto settle = [&](size_t from) {                       // downloads in flight write into `sets`
@@ -657,6 +831,34 @@ void Decoder::worker() {
       const auto t0 = now();
       int st = done[f].get();
       if (!st && vpcc_gof_download_wait(cur.part[f % G].g, (uint32_t)(f / G)) != VPCC_OK) { st = VPCC_ERR_DEVICE; derr[f] = "download failed"; }
+      if (!st && f == flip_f && !(V & VPCC_VERIFY_DELIVERY) && sets[f].len())      // tests only (verified: the pool's job flips it)
+        reinterpret_cast<unsigned char*>(sets[f].positions.data())[0] ^= 1u;
+      if (!st && V) {
+        // the checks of this frame: a mismatch ends the stream in front of it
+        const Part& P = cur.part[f % G];
+        const size_t local = f / G, nl = P.frames.size();
+        const uint64_t index = cur.first_index + f;
+        auto check = [&](uint32_t flag, const char* stage, uint64_t expected, uint64_t got, uint64_t* passed) {
+          if (!(V & flag) || st) return;
+          if (expected == got) { ++*passed; return; }
+          char b[160];
+          std::snprintf(b, sizeof b, "verify: %s mismatch at frame %llu (expected 0x%016llx, got 0x%016llx)", stage,
+                        (unsigned long long)index, (unsigned long long)expected, (unsigned long long)got);
+          derr[f] = b;
+          st = VPCC_ERR_DEVICE;
+        };
+        if (V & VPCC_VERIFY_INGEST) check(VPCC_VERIFY_INGEST, "ingest", cur.host_planes[f].get(), P.dig[vpcc::kSlotPlanes * nl + local], &vstats_.ingest_frames);
+        if (V & VPCC_VERIFY_RECONSTRUCT)
+          check(VPCC_VERIFY_RECONSTRUCT, "reconstruct", P.check_dig[vpcc::kSlotOutputs * nl + local], P.dig[vpcc::kSlotOutputs * nl + local],
+                &vstats_.reconstruct_frames);
+        if (V & VPCC_VERIFY_DELIVERY) {
+          const uint64_t h = delivered[f].get();
+          check(VPCC_VERIFY_DELIVERY, "delivery", P.dig[vpcc::kSlotOutputsSmoothed * nl + local], h, &vstats_.delivery_frames);
+          sets[f].digest = h;
+          sets[f].has_digest = true;
+        }
+        if (vpool) vstats_.host_seconds = vpool->seconds();
+      }
       const auto t1 = now();
       t_download += secs(t0, t1);
       bool sent = false;
@@ -852,6 +1054,29 @@ extern "C" double vpcc_decoder_first_frame_seconds(const vpcc_decoder* d) { retu
 extern "C" int vpcc_decoder_stats(const vpcc_decoder* d, vpcc_decoder_stats_t* out) {
   if (!d || !out) return VPCC_ERR_INVALID_ARG;
   *out = d->made ? d->made->stats() : vpcc_decoder_stats_t{};
+  return VPCC_OK;
+}
+
+extern "C" int vpcc_decoder_set_verify(vpcc_decoder* d, uint32_t flags) {
+  if (!d) return VPCC_ERR_INVALID_ARG;
+  if (d->started) { d->err = "vpcc_decoder_set_verify after vpcc_decoder_start"; return VPCC_ERR_STATE; }
+  if (flags & ~VPCC_VERIFY_ALL) { d->err = "vpcc_decoder_set_verify: unknown flags"; return VPCC_ERR_INVALID_ARG; }
+  d->params.verify = flags;
+  d->params.verify_from_env = false;
+  return VPCC_OK;
+}
+
+extern "C" int vpcc_decoder_frame_digest(vpcc_decoder* d, uint64_t* out) {
+  if (!d || !out) return VPCC_ERR_INVALID_ARG;
+  if (!d->cur || !d->cur->has_digest) return VPCC_ERR_STATE;     // no frame yet, or no delivery check
+  *out = d->cur->digest;
+  return VPCC_OK;
+}
+
+extern "C" int vpcc_decoder_verify_stats(const vpcc_decoder* d, vpcc_decoder_verify_stats_t* out) {
+  if (!d || !out) return VPCC_ERR_INVALID_ARG;
+  *out = d->made ? d->made->verify_stats() : vpcc_decoder_verify_stats_t{};
+  if (!d->made) out->flags = d->params.verify_from_env ? 0u : d->params.verify;
   return VPCC_OK;
 }
 

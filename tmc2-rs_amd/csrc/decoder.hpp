@@ -49,6 +49,10 @@ struct Params {                       // src/lib.rs:23-57
   // Inputs that carry no SEI (a .vpccgof container): geometry smoothing with these parameters when the switch is on
   // and grid_size >= 2 (geometry_bitdepth_3d, grid_size, threshold).
   vpcc_smoothing_params geo_smoothing_without_sei{};
+  // Verified mode (extension, vpcc_decoder_set_verify): VPCC_VERIFY_* checks a frame passes before it is handed over.
+  // verify_from_env: not set by the caller — start() reads VPCC_DECODER_VERIFY.
+  uint32_t verify = 0;
+  bool verify_from_env = true;
   explicit Params(std::string path = {}) : compressed_stream_path(std::move(path)) {}
 };
 
@@ -94,6 +98,8 @@ struct PointSet3 {                    // src/codec.rs:20-36 (public part)
   PinnedVec<vpcc_point3> positions;
   PinnedVec<vpcc_color3> colors;
   bool with_colors = false;
+  uint64_t digest = 0;                // verified mode with VPCC_VERIFY_DELIVERY: the output digest of the arrays above
+  bool has_digest = false;
   size_t len() const { return positions.size(); }
 };
 
@@ -185,6 +191,8 @@ class Decoder {
   const std::string& last_error() const { return error_; }   // extension: why the stream ended early
   using Stats = vpcc_decoder_stats_t;         // launches, frames per launch, kernel time, lane affinity (vpcc_recon.h)
   Stats stats() const { return stats_; }      // complete once recv_frame() has returned nullopt
+  using VerifyStats = vpcc_decoder_verify_stats_t;
+  VerifyStats verify_stats() const { return vstats_; }   // likewise
 
   struct iterator {                           // impl Iterator for Decoder, src/lib.rs:148-154
     Decoder* d;
@@ -209,6 +217,10 @@ class Decoder {
   bool started_ = false;
   std::string error_;
   Stats stats_{};
+  VerifyStats vstats_{};
+  // VPCC_DECODER_TEST_CORRUPT=<stage>:<frame> (tests only, read by start()): stage 1 ingest, 2 reconstruct, 3 delivery; 0 none
+  int corrupt_stage_ = 0;
+  uint64_t corrupt_frame_ = 0;
 };
 
 enum class Format { Ascii, BinaryLittleEndian };   // src/writer.rs:8-12 (the binary variant is commented out there)

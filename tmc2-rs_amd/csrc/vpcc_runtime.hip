@@ -62,6 +62,7 @@ extern "C" void vpcc_ctx_destroy(vpcc_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   for (auto& a : ctx->arena_cache) (void)hipFree(a.first);
   for (auto& a : ctx->stage_cache) (void)hipHostFree(a.first);
+  for (auto& b : ctx->digest_cache) { (void)hipFree(b.dev); (void)hipHostFree(b.host); }
   for (auto& b : ctx->lent) release_block(ctx, b);          // (what a producer still holds goes with the context)
   ctx->lent.clear();
   retire_pool(ctx);

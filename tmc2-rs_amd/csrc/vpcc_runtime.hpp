@@ -53,6 +53,9 @@ struct vpcc_ctx {
   bool pool_pending = false;                             // a vpcc_ctx_reserve is under way
   std::vector<Block> block_cache;                        // big blocks of destroyed gofs that are allocations of their own
   std::vector<Block> lent;                               // vpcc_ctx_pool_alloc: blocks a producer of device planes holds
+  // Frame digests (vpcc_digest.hip): a gof's slots on the device and their page-locked copy, kept for the next gof that asks
+  struct DigestBuffers { void* dev = nullptr; void* host = nullptr; size_t bytes = 0; };
+  std::vector<DigestBuffers> digest_cache;
 };
 
 struct KernelTiming {
@@ -117,6 +120,17 @@ struct vpcc_gof {
   bool smooth_clean = false;           // the scratch is all-zero (the invariant between launches)
   void* smooth_keys = nullptr;         // the cell lists of every chunk of 256 points of every frame, then their lengths
   void* smooth_moved = nullptr;        // both filters in one pass: which points moved (a bit each), and the cell each was counted in
+  // Frame digests (vpcc_digest.hip), on demand: kDigestSlots x n_frames words on the device and a page-locked copy of them.
+  // The digest kernels are ordered in front of results_ready once the gof has been launched; the destructor (vpcc_digest.hip)
+  // waits for the last of them and gives the buffers back to the context's cache.
+  struct DigestState {
+    vpcc_ctx* ctx = nullptr;
+    vpcc_ctx::DigestBuffers bufs;
+    hipEvent_t ready = nullptr;                // behind the last digest kernel
+    std::vector<KernelTiming> timing;          // profile mode: event pairs of the digest kernels since the last read
+    uint32_t timed = 0;
+    ~DigestState();
+  } digest;
 };
 
 namespace vpcc {

@@ -40,6 +40,11 @@ VPCC_GOF_PROFILE = 0x4
 VPCC_GOF_ASYNC_UPLOAD = 0x8
 VPCC_GOF_COPY_PLANES = 0x20
 
+VPCC_VERIFY_INGEST = 0x1
+VPCC_VERIFY_RECONSTRUCT = 0x2
+VPCC_VERIFY_DELIVERY = 0x4
+VPCC_VERIFY_ALL = 0x7
+
 ORIENT_DEFAULT, ORIENT_SWAP, ORIENT_ROT90, ORIENT_ROT180, ORIENT_ROT270 = 0, 1, 2, 3, 4
 ORIENT_MIRROR, ORIENT_MROT90, ORIENT_MROT180, ORIENT_MROT270 = 5, 6, 7, 8
 
@@ -188,6 +193,13 @@ class V3cGofInfo(C.Structure):
         "smoothing_threshold", "reserved")] + [("video_bytes", C.c_size_t * 3)]
 
 
+class VerifyStats(C.Structure):
+    """vpcc_decoder_verify_stats_t (include/vpcc_recon.h)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("ingest_frames", C.c_uint64),
+                ("reconstruct_frames", C.c_uint64), ("delivery_frames", C.c_uint64), ("host_seconds", C.c_double),
+                ("kernel_seconds", C.c_double)]
+
+
 def load_library():
     """Loads libvpcc_recon.so (built in-tree by `make` / __graft_entry__.build()).
     Raises — never falls back — when it is missing."""
@@ -257,6 +269,13 @@ def load_library():
     lib.vpcc_decoder_stats.argtypes = [vp, C.POINTER(DecoderStats)]
     lib.vpcc_ctx_bind_thread.argtypes = [vp, C.POINTER(C.c_int)]
     lib.vpcc_decoder_close.argtypes = [vp]
+    lib.vpcc_digest_points.argtypes = [vp, vp, sz, C.POINTER(u64)]
+    lib.vpcc_digest_frame_planes.argtypes = [FD, C.POINTER(u64)]
+    lib.vpcc_gof_output_digests.argtypes = [vp, u32, u32, vp]
+    lib.vpcc_gof_plane_digests.argtypes = [vp, u32, u32, vp]
+    lib.vpcc_decoder_set_verify.argtypes = [vp, u32]
+    lib.vpcc_decoder_frame_digest.argtypes = [vp, C.POINTER(u64)]
+    lib.vpcc_decoder_verify_stats.argtypes = [vp, C.POINTER(VerifyStats)]
     lib.vpcc_decoder_close.restype = None
     lib.vpcc_write_ply.argtypes = [C.c_char_p, vp, vp, sz]
     lib.vpcc_write_ply_format.argtypes = [C.c_char_p, vp, vp, sz, C.c_int]

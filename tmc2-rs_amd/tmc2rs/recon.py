@@ -29,6 +29,52 @@ def validate_frame(frame):
     return lib.vpcc_frame_validate(C.byref(desc))
 
 
+def digest_points(xyz, rgb=None):
+    """vpcc_digest_points: the output digest (include/vpcc_recon.h) of n points — xyz an (n, 3) uint16 array, rgb an (n, 3)
+    uint8 array or None (a frame without colours).  Host code, no GPU needed."""
+    lib = _abi.load_library()
+    xyz = np.ascontiguousarray(xyz, dtype=np.uint16).reshape(-1, 3)
+    n = xyz.shape[0]
+    if rgb is not None:
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
+        if rgb.shape[0] != n:
+            raise ValueError("xyz and rgb differ in length")
+    out = C.c_uint64(0)
+    st = lib.vpcc_digest_points(xyz.ctypes.data if n else None, rgb.ctypes.data if rgb is not None else None, n,
+                                C.byref(out))
+    if st:
+        raise VpccError(st, "vpcc_digest_points")
+    return out.value
+
+
+def digest_planes(frame):
+    """vpcc_digest_frame_planes: the plane digest of a frame dict (host planes).  Host code, no GPU needed."""
+    lib = _abi.load_library()
+    desc, keep = host_frame_desc(frame)
+    out = C.c_uint64(0)
+    st = lib.vpcc_digest_frame_planes(C.byref(desc), C.byref(out))
+    if st:
+        raise VpccError(st, "vpcc_digest_frame_planes")
+    return out.value
+
+
+def verify_flags(verify):
+    """Decoder(verify=...): None / 0 (off), an int of VPCC_VERIFY_* bits, or a string "ingest,reconstruct,delivery" / "all"."""
+    if not verify:
+        return 0
+    if isinstance(verify, int):
+        return verify
+    names = {"ingest": _abi.VPCC_VERIFY_INGEST, "reconstruct": _abi.VPCC_VERIFY_RECONSTRUCT,
+             "delivery": _abi.VPCC_VERIFY_DELIVERY, "all": _abi.VPCC_VERIFY_ALL}
+    flags = 0
+    for w in str(verify).replace("|", ",").split(","):
+        w = w.strip()
+        if w not in names:
+            raise ValueError(f"unknown verify stage {w!r}")
+        flags |= names[w]
+    return flags
+
+
 class Context:
     """vpcc_ctx: one per GPU / worker thread."""
 
@@ -246,6 +292,20 @@ class Gof:
         n = self.lib.vpcc_gof_kernel_time_means(self.h, int(last_n), names, ms, C.byref(launches), 16)
         return {names[i].decode(): float(ms[i]) for i in range(n)}, launches.value
 
+    def _digests(self, fn, first, count, where):
+        count = self.n_frames - first if count is None else count
+        out = np.zeros(max(count, 1), dtype=np.uint64)
+        self.ctx._check(fn(self.h, first, count, out.ctypes.data), where)
+        return out[:count]
+
+    def output_digests(self, first=0, count=None):
+        """vpcc_gof_output_digests: the output digest of every frame of [first, first+count), behind the gof's launches."""
+        return self._digests(self.lib.vpcc_gof_output_digests, first, count, "vpcc_gof_output_digests")
+
+    def plane_digests(self, first=0, count=None):
+        """vpcc_gof_plane_digests: the plane digest of every frame of [first, first+count) over its device planes."""
+        return self._digests(self.lib.vpcc_gof_plane_digests, first, count, "vpcc_gof_plane_digests")
+
     def algorithmic_bytes(self, frame):
         b = C.c_uint64(0)
         self.ctx._check(self.lib.vpcc_gof_algorithmic_bytes(self.h, frame, C.byref(b)), "vpcc_gof_algorithmic_bytes")
@@ -257,8 +317,10 @@ class Decoder:
     Iterator, src/lib.rs:70-154).  Iterating yields dicts {n, xyz, rgb} in presentation order."""
 
     def __init__(self, path, devices=(0,), occupancy_yuv=None, geometry_yuv=None, attribute_yuv=None,
-                 occupancy_precision=4):
-        """`path`: a .vpccgof container, or — with the raw decoded videos given — a V3C sample stream (.bin)."""
+                 occupancy_precision=4, verify=None):
+        """`path`: a .vpccgof container, or — with the raw decoded videos given — a V3C sample stream (.bin).
+        `verify`: the verified mode (vpcc_decoder_set_verify) — "ingest,reconstruct,delivery", "all" or VPCC_VERIFY_* bits;
+        None leaves it to the environment (VPCC_DECODER_VERIFY)."""
         self.lib = _abi.load_library()
         self.h = C.c_void_p()
         dev = (C.c_int * len(devices))(*devices)
@@ -270,6 +332,10 @@ class Decoder:
                                                 occupancy_precision, dev, len(devices), C.byref(self.h))
         if st:
             raise VpccError(st, "vpcc_decoder_open")
+        if verify is not None:
+            st = self.lib.vpcc_decoder_set_verify(self.h, verify_flags(verify))
+            if st:
+                raise VpccError(st, "vpcc_decoder_set_verify", self.error())
 
     def set_smoothing(self, geometry=False, color=False, bitdepth=10, grid_size=0, threshold=0, color_grid_size=0,
                       color_threshold_smoothing=0, color_threshold_difference=0):
@@ -303,7 +369,9 @@ class Decoder:
             C.memmove(xyz.ctypes.data, px.value, k * 6)
             if pc.value:
                 C.memmove(rgb.ctypes.data, pc.value, k * 3)
-        return {"n": k, "xyz": xyz, "rgb": rgb if pc.value else None}
+        d = C.c_uint64(0)
+        digest = d.value if self.lib.vpcc_decoder_frame_digest(self.h, C.byref(d)) == 0 else None
+        return {"n": k, "xyz": xyz, "rgb": rgb if pc.value else None, "digest": digest}
 
     def drain(self):
         """Consumes the rest of the stream inside the library; returns (frames, points, seconds)."""
@@ -325,6 +393,15 @@ class Decoder:
         return {"launches": st.launches, "frames": st.frames, "max_frames_per_launch": st.max_frames_per_launch,
                 "lanes": st.lanes, "kernel_seconds": st.kernel_seconds, "launch_seconds": st.launch_seconds,
                 "numa_node": list(st.numa_node)[:st.lanes]}
+
+    def verify_stats(self):
+        """vpcc_decoder_verify_stats: flags in force, frames that passed each check, host hashing and check-kernel seconds."""
+        st = _abi.VerifyStats()
+        rc = self.lib.vpcc_decoder_verify_stats(self.h, C.byref(st))
+        if rc:
+            raise VpccError(rc, "vpcc_decoder_verify_stats")
+        return {"flags": st.flags, "ingest_frames": st.ingest_frames, "reconstruct_frames": st.reconstruct_frames,
+                "delivery_frames": st.delivery_frames, "host_seconds": st.host_seconds, "kernel_seconds": st.kernel_seconds}
 
     def __iter__(self):
         return self

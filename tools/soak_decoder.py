@@ -2,7 +2,8 @@
 """Soak of the streaming Decoder: random streams — 1 .. 14 GOFs of 1 .. 40 frames drawn from a pool of random frames of several canvas
 sizes —, 1 .. 4 lanes (on one GPU), random ingest switches (stretches / kernel / copy engine, staged descriptors or not, the input
 page-locked in chunks, with or without the tail split, with or without a pool), now and then a consumer that stops early, three streams in ten with the smoothing filters switched on (random parameters); every
-frame that arrives is compared with the oracle's (and the smoothing specification's), in presentation order; of a stream that differs the
+frame that arrives is compared with the oracle's (and the smoothing specification's), in presentation order, and the Decoder runs verified (verify="all":
+a frame that goes wrong on the device ends the stream with an error naming the stage); of a stream that differs the
 tool prints which frames, points and values, and decodes the same file three more times.  Usage: tools/soak_decoder.py [streams = 150] [first seed = 0]
 Environment: VPCC_SOAK_SHORT_STREAMS=1 — 1-3 GOFs of 1-8 frames (the start of a stream, over and over: seven streams a second);
 VPCC_SOAK_FORCE_SWITCHES=A,B — these switches on in every stream (a hunt in one configuration)."""
@@ -77,7 +78,7 @@ try:
         lanes = int(rng.choice([1, 1, 2, 3, 4]))
         stop_at = int(rng.integers(0, len(expect))) if rng.random() < 0.15 else None
         container.write_container(path, gofs)
-        dec = recon.Decoder(path, devices=(0,) * lanes)
+        dec = recon.Decoder(path, devices=(0,) * lanes, verify="all")     # a wrong frame ends the stream, naming its stage
         if sm is not None:
             dec.set_smoothing(geometry=sm[0], color=sm[1], bitdepth=10, grid_size=sm[2], threshold=sm[3], color_grid_size=sm[4],
                               color_threshold_smoothing=sm[5], color_threshold_difference=sm[6])
@@ -105,7 +106,8 @@ try:
             differ = [i for i, (a, b) in enumerate(zip(got, expect)) if a != b]
             print(f"MISMATCH stream {si}: {len(gofs)} GOFs of {[len(g) for g in gofs]} frames, {lanes} lanes, {on}, "
                   f"{ {k: os.environ[k] for k in ('VPCC_DECODER_PIN_CHUNK_MB', 'VPCC_DECODER_POOL_GIB') if k in os.environ} }, smoothing {sm}, stop_at {stop_at}: "
-                  f"error {err!r}, {len(got)} of {len(expect)} frames, first difference at {first}", flush=True)
+                  f"error {err!r}, {len(got)} of {len(expect)} frames, first difference at {first}, "
+                  f"verify stage {err.split()[1] if err.startswith('verify:') else '-'}", flush=True)
             for line in detail[:8]:
                 print("  " + line, flush=True)
             # which frames, what they are, and whether the same stream decoded again differs again
