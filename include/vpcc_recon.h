@@ -124,6 +124,28 @@ typedef struct vpcc_frame_desc {
                                    convert_yuv16_to_rgb8 (src/decoder.rs:301-305); unreachable in
                                    the reference (format is always Yuv420) — rejected as UNSUPPORTED */
 
+/* Planes from a hardware video decoder: P010 / P016 semi-planar surfaces (rocDecode, NVDEC, VA-API, FFmpeg
+ * p010le).  All-zero bits below: the planar yuv420p10le layout above, exactly as before.
+ *
+ * VPCC_FRAME_UV_INTERLEAVED: the attribute chroma of each map is ONE plane of interleaved U,V,U,V... samples.
+ *   attribute[m].u points at it and attribute[m].v MUST be NULL (a library that predates this flag refuses such a
+ *   descriptor with VPCC_ERR_SHORT_VIDEO); attribute[m].cstride is its row stride in u16 ELEMENTS, >= 2*(width/2).
+ *   Pixel (x, y) takes U from uv[(y/2)*cstride + 2*(x/2)] and V from the element after it — the reference's
+ *   nearest-neighbour rule (src/decoder.rs:977) on the interleaved plane.
+ * VPCC_FRAME_GEO_SHIFT(s) / VPCC_FRAME_ATTR_SHIFT(s), s in 0..8: every geometry / attribute sample is read as
+ *   sample >> s before anything else uses it (depth = (sample >> s) >> 2, the D1 rules, the YUV -> RGB conversion);
+ *   the discarded low bits may hold anything.  MSB-aligned 10-bit content (P010 / P016) is s = 6.  s > 8:
+ *   VPCC_ERR_INVALID_ARG.
+ * Occupancy is untouched: the luma of an 8-bit NV12 surface is a u8 plane with a pitch, which `occupancy` already takes.
+ * All frames of one gof agree on these bits (else vpcc_gof_create fails with VPCC_ERR_UNSUPPORTED).
+ * A rocDecode / VA-API P016 surface of pitch P bytes whose chroma starts at byte offset C maps to
+ *   y = base, stride = P / 2;  u = base + C, v = NULL, cstride = P / 2;  flags = VPCC_FRAME_UV_INTERLEAVED |
+ *   VPCC_FRAME_GEO_SHIFT(6) | VPCC_FRAME_ATTR_SHIFT(6)  (geometry: the luma plane only). */
+#define VPCC_FRAME_UV_INTERLEAVED 0x2u
+#define VPCC_FRAME_GEO_SHIFT(s)   ((uint32_t)(s) << 8)    /* bits 8-11  */
+#define VPCC_FRAME_ATTR_SHIFT(s)  ((uint32_t)(s) << 12)   /* bits 12-15 */
+#define VPCC_FRAME_LAYOUT_MASK    0xFF02u                 /* the bits all frames of a gof must agree on */
+
 /* Where the plane pointers of a vpcc_frame_desc live. */
 typedef enum vpcc_memory_kind {
   VPCC_MEM_HOST = 0,    /* host pointers: the library stages them into HBM (H2D)   */
@@ -407,7 +429,9 @@ int vpcc_gof_smooth(vpcc_gof* gof, uint32_t first, uint32_t count, const vpcc_sm
  * Plane digest of a frame: head = (width << 32) | height; only the logical elements of each plane, never stride padding;
  * u16 values little endian.  p = 0: the occupancy rows, y < occ_h, each occ_w bytes; p = 1 + m: geometry luma of map m,
  * `height` rows of 2·width bytes; p = 3 + 3m + c, for c = Y, U, V: attribute planes of map m when attribute_count is
- * non-zero — Y is width × height, U and V are (width/2) × (height/2).
+ * non-zero — Y is width × height, U and V are (width/2) × (height/2).  With VPCC_FRAME_UV_INTERLEAVED map m's chroma is
+ * ONE row set p = 4 + 3m of height/2 rows of 4·(width/2) bytes — the interleaved U,V pairs — and there are no p = 5 + 3m
+ * rows.  Samples are hashed as stored, before any VPCC_FRAME_*_SHIFT: the digest is of the planes as delivered.
  *
  * mix64 is a bijection, so changing any single 8-byte word always changes the digest; the sum commutes, so the order of a
  * GPU reduction cannot change it; the position (p, y, k) enters every term, so reordered points change it except with
@@ -451,6 +475,13 @@ int vpcc_decoder_open_v3c(const char* bin_path, const char* occupancy_yuv, const
  * this library's own specification (vpcc_gof_smooth); frames are delivered smoothed.  `params` may be NULL. */
 int  vpcc_decoder_set_smoothing(vpcc_decoder* dec, int apply_geo_smoothing, int apply_attr_smoothing,
                                 const vpcc_smoothing_params* params);
+/* Layout of the geometry and attribute raw files of vpcc_decoder_open_v3c.  Between open and start (after start:
+ * VPCC_ERR_STATE); a decoder opened with vpcc_decoder_open (a .vpccgof container) or an unknown format:
+ * VPCC_ERR_INVALID_ARG.  A P010LE frame has the byte size of a planar one; the occupancy file stays 8-bit 4:2:0 (only
+ * its luma is read, and yuv420p and nv12 share it). */
+#define VPCC_VIDEO_YUV420P10LE 0   /* the default: planar, 10 bits in [9:0]                                              */
+#define VPCC_VIDEO_P010LE      1   /* per frame W x H u16 luma, then H/2 rows of W u16 interleaved U,V; 10 bits in [15:6] */
+int  vpcc_decoder_set_video_format(vpcc_decoder* dec, int format);
 int  vpcc_decoder_start(vpcc_decoder* dec);
 /* 1 and the next frame (pointers valid until the next call), or 0 at end of stream — also after a
  * failure in the worker, like the reference's consumer sees None after a worker panic. */

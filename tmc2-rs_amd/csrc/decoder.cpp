@@ -345,7 +345,7 @@ void Decoder::start() {
     const size_t a0 = file_.size(), an = params_.attribute_yuv_path.empty() ? 0 : slurp(params_.attribute_yuv_path, &file_, a0);
     int status = 0;
     if (!parse_v3c_with_raw_video(bin_, file_.data() + o0, on, file_.data() + g0, gn, file_.data() + a0, an,
-                                  params_.occupancy_precision, &gofs_, &err, &status))
+                                  params_.occupancy_precision, &gofs_, &err, &status, params_.video_format))
       throw std::runtime_error(std::string(vpcc_status_string(status)) + ": " + err);
   }
   thread_ = std::thread([this] { worker(); });
@@ -471,7 +471,8 @@ void Decoder::worker() {
           if (fr.attribute_count) {
             plane(fr.attribute[m].y, (size_t)fr.attribute[m].stride * fr.attribute[m].height * 2);
             plane(fr.attribute[m].u, (size_t)fr.attribute[m].cstride * ((fr.attribute[m].height + 1) / 2) * 2);
-            plane(fr.attribute[m].v, (size_t)fr.attribute[m].cstride * ((fr.attribute[m].height + 1) / 2) * 2);
+            if (fr.attribute[m].v)                    // (null: interleaved chroma, P010LE — the one plane is `u`)
+              plane(fr.attribute[m].v, (size_t)fr.attribute[m].cstride * ((fr.attribute[m].height + 1) / 2) * 2);
           }
         }
       }
@@ -999,6 +1000,21 @@ extern "C" int vpcc_decoder_set_smoothing(vpcc_decoder* d, int apply_geo_smoothi
     d->params.attr_smoothing = *params;
     d->params.geo_smoothing_without_sei = *params;
   }
+  return VPCC_OK;
+}
+
+extern "C" int vpcc_decoder_set_video_format(vpcc_decoder* d, int format) {
+  if (!d) return VPCC_ERR_INVALID_ARG;
+  if (d->started) { d->err = "vpcc_decoder_set_video_format after vpcc_decoder_start"; return VPCC_ERR_STATE; }
+  if (d->params.occupancy_yuv_path.empty()) {          // a .vpccgof container: its planes carry no layout to choose
+    d->err = "vpcc_decoder_set_video_format: the decoder reads a .vpccgof container, not raw video";
+    return VPCC_ERR_INVALID_ARG;
+  }
+  if (format != VPCC_VIDEO_YUV420P10LE && format != VPCC_VIDEO_P010LE) {
+    d->err = "vpcc_decoder_set_video_format: unknown format";
+    return VPCC_ERR_INVALID_ARG;
+  }
+  d->params.video_format = format;
   return VPCC_OK;
 }
 

@@ -37,6 +37,9 @@ struct Params {                       // src/lib.rs:23-57
   std::string occupancy_yuv_path, geometry_yuv_path, attribute_yuv_path;
   uint32_t occupancy_precision = 4;   // frame_width / occupancy video width (the reference derives it from
                                       // the decoded video, src/decoder.rs:194; a raw file carries no size)
+  // Layout of the geometry and attribute raw files (vpcc_decoder_set_video_format): VPCC_VIDEO_YUV420P10LE (planar, the
+  // default) or VPCC_VIDEO_P010LE (a hardware decoder's semi-planar, MSB-aligned output: same bytes per frame)
+  int video_format = VPCC_VIDEO_YUV420P10LE;
   // Post-processing switches of the reference's Params (src/lib.rs:45-46: private and always false there, and
   // `unimplemented!()` behind them, src/decoder.rs:291-299).  Geometry smoothing runs when the switch is on AND the GOF
   // carries a geometry-smoothing SEI (src/decoder.rs:291, 630-637): grid size and threshold are the SEI's.  The
@@ -174,7 +177,8 @@ struct DecodedGof {
 // offsets (see Params).  Returns false + message on error; *status receives the vpcc_status of a syntax error.
 bool parse_v3c_with_raw_video(const std::vector<unsigned char>& bin, const unsigned char* occ, size_t occ_bytes,
                               const unsigned char* geo, size_t geo_bytes, const unsigned char* attr, size_t attr_bytes,
-                              uint32_t occupancy_precision, std::vector<DecodedGof>* gofs, std::string* err, int* status);
+                              uint32_t occupancy_precision, std::vector<DecodedGof>* gofs, std::string* err, int* status,
+                              int video_format = VPCC_VIDEO_YUV420P10LE);
 
 // Parses a .vpccgof container held in `buf` (kept alive by the caller).  Returns false + message on error.
 bool parse_container(const std::vector<unsigned char>& buf, std::vector<DecodedGof>* gofs, std::string* err);

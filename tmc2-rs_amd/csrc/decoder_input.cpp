@@ -97,7 +97,8 @@ bool parse_container(const std::vector<unsigned char>& buf, std::vector<DecodedG
 // (src/codec.rs:317, 589-590).
 bool parse_v3c_with_raw_video(const std::vector<unsigned char>& bin, const unsigned char* occ, size_t occ_bytes,
                               const unsigned char* geo, size_t geo_bytes, const unsigned char* attr, size_t attr_bytes,
-                              uint32_t occupancy_precision, std::vector<DecodedGof>* gofs, std::string* err, int* status) {
+                              uint32_t occupancy_precision, std::vector<DecodedGof>* gofs, std::string* err, int* status,
+                              int video_format) {
   *status = VPCC_ERR_INVALID_ARG;
   gofs->clear();
   if (occupancy_precision == 0) { *err = "occupancy_precision is zero"; return false; }
@@ -135,6 +136,9 @@ bool parse_v3c_with_raw_video(const std::vector<unsigned char>& bin, const unsig
     const size_t luma = (size_t)W * H * 2, chroma = (size_t)(W / 2) * (H / 2) * 2;
     const size_t vid_frame = luma + 2 * chroma;
     const bool has_attr = !syn.vps.ai.attributes.empty();
+    // P010LE: the luma, then H/2 rows of W interleaved U,V samples — the bytes of the planar U and V planes together — with the
+    // 10 significant bits in [15:6] (vpcc_recon.h, VPCC_FRAME_UV_INTERLEAVED and the sample shifts)
+    const bool p010 = video_format == VPCC_VIDEO_P010LE;
     DecodedGof gof;
     gof.has_syntax = true;
     if (gp.geometry_smoothing_sei && gp.smoothing_grid_size >= 2) {      // SeiGeometrySmoothing, src/bitstream/reader.rs:1452-1505
@@ -152,6 +156,7 @@ bool parse_v3c_with_raw_video(const std::vector<unsigned char>& bin, const unsig
       d.map_count = gp.map_count;
       d.absolute_d1 = gp.absolute_d1 ? 1u : 0u;
       d.attribute_count = has_attr ? 1u : 0u;
+      if (p010) d.flags = VPCC_FRAME_UV_INTERLEAVED | VPCC_FRAME_GEO_SHIFT(6) | VPCC_FRAME_ATTR_SHIFT(6);
       gof.patch_store.push_back(std::move(frames[f].patches));
       d.patch_count = (uint32_t)gof.patch_store.back().size();
       d.patches = d.patch_count ? gof.patch_store.back().data() : nullptr;
@@ -165,8 +170,10 @@ bool parse_v3c_with_raw_video(const std::vector<unsigned char>& bin, const unsig
         if (has_attr) {
           if (attr_off + vid_frame > attr_bytes) { *err = "attribute video shorter than the atlas"; *status = VPCC_ERR_SHORT_VIDEO; return false; }
           const unsigned char* a = attr + attr_off;
-          d.attribute[m] = vpcc_image_u16{reinterpret_cast<const uint16_t*>(a), reinterpret_cast<const uint16_t*>(a + luma),
-                                          reinterpret_cast<const uint16_t*>(a + luma + chroma), W, H, W, W / 2};
+          d.attribute[m] = p010 ? vpcc_image_u16{reinterpret_cast<const uint16_t*>(a), reinterpret_cast<const uint16_t*>(a + luma),
+                                                 nullptr, W, H, W, W}
+                                : vpcc_image_u16{reinterpret_cast<const uint16_t*>(a), reinterpret_cast<const uint16_t*>(a + luma),
+                                                 reinterpret_cast<const uint16_t*>(a + luma + chroma), W, H, W, W / 2};
           attr_off += vid_frame;
         }
       }

@@ -163,6 +163,8 @@ struct PixelOut {
   uint32_t n;
 };
 
+// kLayout: the frame has VPCC_FRAME_LAYOUT_MASK bits (the sample shifts are read from it; false: planar, no shifts)
+template <bool kLayout>
 __device__ __forceinline__ PixelOut eval_pixel(const DevFrame& f, const VBlock& b, uint32_t pu, uint32_t pv) {
   PixelOut o;
   o.n = 0;
@@ -179,8 +181,9 @@ __device__ __forceinline__ PixelOut eval_pixel(const DevFrame& f, const VBlock& 
   // and the pixel's points are built without a branch: with the depths behind `if (occ == 0) return` every occupied pixel paid
   // two dependent round trips to memory, one per plane kind.
   const uint8_t occ = gl(f.occ)[oy * f.occ_stride + ox];                             // src/codec.rs:288-301, 393
-  const uint32_t d0 = (uint32_t)(gl(f.geo[0])[o.y * f.geo_stride[0] + o.x] >> 2);  // depth / 4, codec.rs:534
-  const uint32_t d1 = (uint32_t)(gl(f.geo[1])[o.y * f.geo_stride[1] + o.x] >> 2);  // (one map: the descriptor's alias of layer 0)
+  const uint32_t gs = kLayout ? layout_geo_shift(f.layout) : 0u;                  // VPCC_FRAME_GEO_SHIFT
+  const uint32_t d0 = (uint32_t)(gl(f.geo[0])[o.y * f.geo_stride[0] + o.x] >> gs) >> 2;  // depth / 4, codec.rs:534
+  const uint32_t d1 = (uint32_t)(gl(f.geo[1])[o.y * f.geo_stride[1] + o.x] >> gs) >> 2;  // (one map: the descriptor's alias of layer 0)
   o.p0 = make_point(b, pu, pv, d0);
   o.p1 = o.p0;
   uint32_t n = 1;

@@ -147,7 +147,22 @@ struct DevFrame {
   uint32_t capacity;
   uint32_t n_tiles;           // number of work items, written by the planning kernel (the array is padded to a multiple of 16 readable items)
   uint32_t prec_shift;        // log2(prec) when prec is a power of two (tile kernel)
+  uint32_t layout;            // the frame's VPCC_FRAME_LAYOUT_MASK bits: UV_INTERLEAVED (attr_u is the interleaved chroma plane,
+                              // attr_v is null) | GEO_SHIFT | ATTR_SHIFT.  (Fills what was padding: sizeof and every other offset as before.)
 };
+static_assert(sizeof(DevFrame) == 288, "DevFrame keeps its size: the planar kernels' frame stride");
+VPCC_HD inline uint32_t layout_geo_shift(uint32_t layout) { return (layout >> 8) & 15u; }
+VPCC_HD inline uint32_t layout_attr_shift(uint32_t layout) { return (layout >> 12) & 15u; }
+VPCC_HD inline bool layout_uv(uint32_t layout) { return (layout & VPCC_FRAME_UV_INTERLEAVED) != 0; }
+// Instantiations of the tile kernel by the gof's layout (all frames of a gof share it: vpcc_gof_create)
+enum TileLayout : uint32_t {
+  kTilePlanar = 0,            // yuv420p10le planes, no shifts: the kernel as it always was
+  kTileShifted = 1,           // planar chroma, shifted samples
+  kTileSurface = 2            // interleaved chroma (P010 / P016), shifted samples
+};
+inline TileLayout tile_layout_of(uint32_t layout) {
+  return layout_uv(layout) ? kTileSurface : (layout & 0xFF00u) ? kTileShifted : kTilePlanar;
+}
 
 // One grid cell of the smoothing filters (oracle/vpcc_smoothing_spec.h): all-zero = empty.
 // Every field is a SUM, so that a wave updates a cell with ONE atomic instruction (four 64-bit adds: {count, s0},
@@ -308,7 +323,9 @@ inline GenShape gen_shape(uint32_t count, uint32_t groups_per_frame, uint32_t ma
 }
 // block_units: every frame of the launch has FrameShape::block_units (vpcc_host.hpp) — k_general_blocks, whose units are chunks
 // of ONE virtual block each, so that everything a block decides is scalar work; else k_general, which takes any frame.
-void launch_general(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_units, uint32_t gen, bool block_units, void* stream);
+// layout: the frames carry VPCC_FRAME_LAYOUT_MASK bits (shifted samples, interleaved chroma): the kernels' instantiation that reads them.
+void launch_general(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_units, uint32_t gen, bool block_units,
+                    bool layout, void* stream);
 // Where the workgroups of one tile-kernel launch start (kernel argument, by value).  A workgroup stays with its
 // frame; frames differ in size (S-longdress +-5 %, S-owlii +-11 % between the largest frame and the mean), so the
 // resident workgroups of an XCD are shared out among its frames in proportion to their tile counts instead of
@@ -323,7 +340,7 @@ struct TileLaunchMap {
 // weights[i]: tiles of frame first + i.  resident_per_xcd: workgroups of this kernel an XCD holds at a time.
 void plan_tile_launch(const uint32_t* tiles, uint32_t count, uint32_t resident_per_xcd, uint32_t depth, TileLaunchMap& map);
 void launch_tiles(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_groups, uint32_t gen,
-                  const TileLaunchMap& map, uint32_t resident_per_xcd,
+                  const TileLaunchMap& map, uint32_t resident_per_xcd, TileLayout layout,
                   void* stream);
 // One piece of the plane ingest by kernel (k_ingest_planes): `bytes` (<= 64 KB) of page-locked host memory, through its
 // device-visible address, to device memory; src and dst are congruent modulo 16.

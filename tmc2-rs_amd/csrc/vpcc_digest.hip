@@ -54,13 +54,15 @@ __device__ inline void wave_add(uint64_t v, unsigned long long* slot) {
 }
 
 // One frame per blockIdx.y.  Its rows, in order: occupancy (occ_h), then per map geometry (H), and with attributes Y (H),
-// U (H/2), V (H/2).  A wave takes one row at a time, its lanes the row's word pairs.
+// U (H/2), V (H/2) — or, interleaved chroma (VPCC_FRAME_UV_INTERLEAVED), the U,V rows (H/2) of attr_u as one row set p = 4 + 3m.
+// A wave takes one row at a time, its lanes the row's word pairs.
 __global__ __launch_bounds__(kDigestThreads) void k_digest_planes(const DevFrame* __restrict__ frames, uint32_t first,
                                                                 unsigned long long* __restrict__ slots) {
   const uint32_t f = first + blockIdx.y;
   const DevFrame& D = frames[f];
   const uint64_t W = D.width, H = D.height;
-  const uint64_t per_map = H + (D.has_attr ? H + 2 * (H / 2) : 0);
+  const bool uv = layout_uv(D.layout);
+  const uint64_t per_map = H + (D.has_attr ? H + (uv ? 1 : 2) * (H / 2) : 0);
   const uint64_t rows = D.occ_h + D.map_count * per_map;
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t waves = (uint64_t)gridDim.x * (kDigestThreads / 64);
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(kDigestThreads) void k_digest_planes(const DevFrame
       } else {
         t -= H;
         const uint64_t c = t / (H / 2);
-        p = 4 + 3 * m + c; y = t % (H / 2); bytes = 2 * (W / 2);
+        p = 4 + 3 * m + c; y = t % (H / 2); bytes = (uv ? 4 : 2) * (W / 2);       // (interleaved: c == 0 only)
         row = (const unsigned char*)((c ? D.attr_v[m] : D.attr_u[m]) + y * D.attr_cstride[m]);
       }
     }
@@ -274,7 +276,7 @@ int gof_device_plane_desc(vpcc_gof* g, uint32_t frame, vpcc_frame_desc* desc) {
     if (!desc->attribute_count) continue;
     desc->attribute[m].y = D.attr_y[m];
     desc->attribute[m].u = D.attr_u[m];
-    desc->attribute[m].v = D.attr_v[m];
+    desc->attribute[m].v = layout_uv(D.layout) ? nullptr : D.attr_v[m];     // (interleaved chroma: the one plane is `u`)
     desc->attribute[m].stride = D.attr_stride[m];
     desc->attribute[m].cstride = D.attr_cstride[m];
   }

@@ -34,6 +34,10 @@ uint64_t digest_frame_planes(const vpcc_frame_desc& f) {
     if (!f.attribute_count) continue;
     const vpcc_image_u16& A = f.attribute[m];
     for (uint64_t y = 0; y < H; ++y) s += digest_row(A.y + y * A.stride, 2 * W, 3 + 3 * m, y);
+    if (f.flags & VPCC_FRAME_UV_INTERLEAVED) {          // one row set of interleaved U,V pairs, as stored
+      for (uint64_t y = 0; y < H / 2; ++y) s += digest_row(A.u + y * A.cstride, 4 * (W / 2), 4 + 3 * m, y);
+      continue;
+    }
     for (uint64_t y = 0; y < H / 2; ++y) s += digest_row(A.u + y * A.cstride, 2 * (W / 2), 4 + 3 * m, y);
     for (uint64_t y = 0; y < H / 2; ++y) s += digest_row(A.v + y * A.cstride, 2 * (W / 2), 5 + 3 * m, y);
   }
@@ -58,6 +62,11 @@ extern "C" int vpcc_digest_frame_planes(const vpcc_frame_desc* f, uint64_t* out)
     if (!G.y || G.stride < f->width || G.width < f->width || G.height < f->height) return VPCC_ERR_INVALID_ARG;
     if (!f->attribute_count) continue;
     const vpcc_image_u16& A = f->attribute[m];
+    if (f->flags & VPCC_FRAME_UV_INTERLEAVED) {
+      if (!A.y || !A.u || A.v || A.stride < f->width || A.cstride < 2 * (f->width / 2) || A.width < f->width || A.height < f->height)
+        return VPCC_ERR_INVALID_ARG;
+      continue;
+    }
     if (!A.y || !A.u || !A.v || A.stride < f->width || A.cstride < f->width / 2 || A.width < f->width || A.height < f->height)
       return VPCC_ERR_INVALID_ARG;
   }

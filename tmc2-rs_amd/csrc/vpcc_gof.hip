@@ -122,7 +122,8 @@ extern "C" int vpcc_gof_reconstruct(vpcc_gof* g, uint32_t first, uint32_t count,
     }
     g->generation = (g->generation % 0x3FFFFFFFu) + 1u;
     T.begin("k_recon_tiles");
-    launch_tiles(g->d_frames, first, count, max_groups, g->generation, g->tile_map, ctx->resident_tile_wgs_per_xcd, s);
+    launch_tiles(g->d_frames, first, count, max_groups, g->generation, g->tile_map, ctx->resident_tile_wgs_per_xcd,
+                 tile_layout_of(g->h_frames[0].layout), s);
     T.end();
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(g->results_ready, s));
@@ -148,7 +149,7 @@ extern "C" int vpcc_gof_reconstruct(vpcc_gof* g, uint32_t first, uint32_t count,
   launch_block_owner(g->d_frames, first, count, max_vb, max_samples, s);
   T.end();
   T.begin(block_units ? "k_general_blocks" : "k_general");
-  launch_general(g->d_frames, first, count, max_units, g->generation, block_units, s);
+  launch_general(g->d_frames, first, count, max_units, g->generation, block_units, g->h_frames[first].layout != 0, s);
   T.end();
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(g->results_ready, s));

@@ -72,6 +72,9 @@ int measure(GofBuild& b, uint64_t capacity_points) {
   for (uint32_t i = 0; i < b.n; ++i) {
     const int st = validate_frame(&b.frames[i], &g->shapes[i]);
     if (st) return fail(b.ctx, st, "frame " + std::to_string(i) + ": " + vpcc_status_string(st));
+    // one plane layout per gof (VPCC_FRAME_UV_INTERLEAVED, the sample shifts): the tile kernel is instantiated per layout
+    if ((b.frames[i].flags ^ b.frames[0].flags) & VPCC_FRAME_LAYOUT_MASK)
+      return fail(b.ctx, VPCC_ERR_UNSUPPORTED, "frame " + std::to_string(i) + ": plane layout differs from frame 0's");
     g->max_vb = std::max(g->max_vb, g->shapes[i].n_vblocks);
     if (capacity_points == 0) cap = std::max<uint64_t>(cap, vpcc_frame_capacity_bound(&b.frames[i]));
   }
@@ -139,12 +142,14 @@ void describe_frame(const GofBuild& b, uint32_t i, char* arena, char* const bloc
   D.map_count = F.map_count; D.absolute_d1 = F.absolute_d1 ? 1u : 0u; D.has_attr = F.attribute_count ? 1u : 0u;
   D.capacity = (uint32_t)b.g->capacity;
   D.occ_w = F.occupancy.width; D.occ_h = F.occupancy.height;
+  D.layout = F.flags & VPCC_FRAME_LAYOUT_MASK;
+  const bool uv = layout_uv(F.flags);                         // P010 / P016: attr_u is the interleaved chroma plane, attr_v null
   if (!b.own_planes) {
     D.occ = F.occupancy.y; D.occ_stride = F.occupancy.stride;
     for (uint32_t m = 0; m < F.map_count; ++m) {
       D.geo[m] = F.geometry[m].y; D.geo_stride[m] = F.geometry[m].stride;
       if (F.attribute_count) {
-        D.attr_y[m] = F.attribute[m].y; D.attr_u[m] = F.attribute[m].u; D.attr_v[m] = F.attribute[m].v;
+        D.attr_y[m] = F.attribute[m].y; D.attr_u[m] = F.attribute[m].u; D.attr_v[m] = uv ? nullptr : F.attribute[m].v;
         D.attr_stride[m] = F.attribute[m].stride; D.attr_cstride[m] = F.attribute[m].cstride;
       }
     }
@@ -157,7 +162,7 @@ void describe_frame(const GofBuild& b, uint32_t i, char* arena, char* const bloc
       if (F.attribute_count) {
         D.attr_y[m] = (const uint16_t*)(planes + o.planes.ay[m]);
         D.attr_u[m] = (const uint16_t*)(planes + o.planes.au[m]);
-        D.attr_v[m] = (const uint16_t*)(planes + o.planes.av[m]);
+        D.attr_v[m] = uv ? nullptr : (const uint16_t*)(planes + o.planes.av[m]);
         D.attr_stride[m] = F.attribute[m].width; D.attr_cstride[m] = F.attribute[m].cstride;
       }
     }
@@ -333,6 +338,11 @@ int enqueue(GofBuild& b) {
       if (F.attribute_count) {
         const vpcc_image_u16& A = F.attribute[m];
         ingest_plane(D.attr_y[m], A.y, 2, A.width, A.height, A.stride);
+        if (layout_uv(F.flags)) {                              // the interleaved plane keeps its stride, like planar chroma
+          const size_t ue = uv_elems(A);
+          ingest_plane(D.attr_u[m], A.u, 2, (uint32_t)ue, 1, (uint32_t)ue);
+          continue;
+        }
         const size_t ce = chroma_elems(A);
         ingest_plane(D.attr_u[m], A.u, 2, (uint32_t)ce, 1, (uint32_t)ce);
         ingest_plane(D.attr_v[m], A.v, 2, (uint32_t)ce, 1, (uint32_t)ce);

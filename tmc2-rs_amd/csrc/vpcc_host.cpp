@@ -52,6 +52,8 @@ int validate_frame(const vpcc_frame_desc* f, FrameShape* shape) {
   if (f->map_count < 1 || f->map_count > 2) return VPCC_ERR_UNSUPPORTED;       // multiple maps > 2 never produced
   if (f->attribute_count > 1) return VPCC_ERR_UNSUPPORTED;                      // src/decoder.rs:133
   if (f->flags & VPCC_FRAME_RGB444) return VPCC_ERR_UNSUPPORTED;                // unreachable in the reference
+  if (layout_geo_shift(f->flags) > 8 || layout_attr_shift(f->flags) > 8) return VPCC_ERR_INVALID_ARG;
+  const bool uv = layout_uv(f->flags);                                          // P010 / P016: one interleaved chroma plane
   if (f->patch_count && !f->patches) return VPCC_ERR_INVALID_ARG;
   if (f->patch_count > 65535) return VPCC_ERR_INVALID_ARG;
   if (!f->occupancy.y || f->occupancy.stride < f->occupancy.width) return VPCC_ERR_INVALID_ARG;
@@ -75,8 +77,9 @@ int validate_frame(const vpcc_frame_desc* f, FrameShape* shape) {
   if (f->attribute_count) {
     for (uint32_t m = 0; m < f->map_count; ++m) {
       const vpcc_image_u16& A = f->attribute[m];
-      if (!A.y || !A.u || !A.v) return VPCC_ERR_SHORT_VIDEO;                    // src/codec.rs:589-590, 637
-      if (A.stride < A.width || A.cstride < A.width / 2) return VPCC_ERR_INVALID_ARG;
+      if (!A.y || !A.u || (!uv && !A.v)) return VPCC_ERR_SHORT_VIDEO;          // src/codec.rs:589-590, 637
+      if (uv && A.v) return VPCC_ERR_INVALID_ARG;                               // the interleaved plane is `u` alone
+      if (A.stride < A.width || A.cstride < (uv ? 2 * (A.width / 2) : A.width / 2)) return VPCC_ERR_INVALID_ARG;
       if ((int64_t)A.width < W || (int64_t)A.height < H) return VPCC_ERR_PATCH_OUT_OF_CANVAS;
       plane_bytes += (uint64_t)A.width * A.height * 2 + 2ull * (A.width / 2) * (A.height / 2) * 2;
     }
@@ -215,6 +218,10 @@ void for_each_plane(const vpcc_frame_desc& F, PlaneSlots& o, Fn&& fn) {
     if (F.attribute_count) {
       fn(F.attribute[m].y, (size_t)F.attribute[m].width * F.attribute[m].height * 2, &o.ay[m], F.attribute[m].stride == F.attribute[m].width);
       // chroma keeps its source stride: the reference indexes it as a flat array (v/2)*(width/2)+(u/2), src/decoder.rs:977
+      if (layout_uv(F.flags)) {                                 // P010 / P016: one interleaved plane, in the U slot
+        fn(F.attribute[m].u, uv_elems(F.attribute[m]) * 2, &o.au[m], true);
+        continue;
+      }
       fn(F.attribute[m].u, chroma_elems(F.attribute[m]) * 2, &o.au[m], true);
       fn(F.attribute[m].v, chroma_elems(F.attribute[m]) * 2, &o.av[m], true);
     }
@@ -379,6 +386,9 @@ void PoolExtents::give_back(uint32_t run, char* ptr, size_t bytes) {
 
 bool tile_planes_aligned(const DevFrame& d) {
   auto al = [](const void* p, uintptr_t a) { return ((uintptr_t)p % a) == 0; };
+#ifdef VPCC_LDS_STAGED_ATTRIBUTES
+  if (d.layout) return false;          // (the experimental tile kernel reads planar, unshifted planes only)
+#endif
   // the lane's occupancy bytes (4 / 2 / 1 for precision 1 / 2 / >= 4) must lie inside one aligned dword
   if (d.prec_shift == 0 && (!al(d.occ, 4) || d.occ_stride % 4)) return false;
   if (d.prec_shift == 1 && (!al(d.occ, 2) || d.occ_stride % 2)) return false;
@@ -397,7 +407,11 @@ bool tile_planes_aligned(const DevFrame& d) {
       return false;
     if (!al(d.geo[m], 8) || d.geo_stride[m] % 4 || d.geo_stride[m] >= (1u << 24)) return false;
     if (d.has_attr && (d.attr_stride[m] >= (1u << 24) || d.attr_cstride[m] >= (1u << 24))) return false;
-    if (d.has_attr) {
+    if (d.has_attr && layout_uv(d.layout)) {
+      // one 8-byte load per lane and layer: U,V of pixels px0, px0 + 2 (px0 a multiple of 4) at ((py0/2)*cstride + px0)*2
+      if (!al(d.attr_y[m], 8) || d.attr_stride[m] % 4) return false;
+      if (!al(d.attr_u[m], 8) || d.attr_cstride[m] % 4) return false;
+    } else if (d.has_attr) {
 #ifdef VPCC_LDS_STAGED_ATTRIBUTES
       // (tools/experiments/vpcc_tiles_lds_dma.hip) attribute tiles reach LDS by 16-byte LDS-DMA pieces: half a luma row /
       // a whole chroma row of a block

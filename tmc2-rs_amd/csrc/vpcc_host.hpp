@@ -57,6 +57,12 @@ inline size_t chroma_elems(const vpcc_image_u16& a) {
   return (size_t)((a.height - 1) / 2) * a.cstride + (a.width - 1) / 2 + 1;
 }
 
+// ... and of an interleaved chroma plane (VPCC_FRAME_UV_INTERLEAVED): U of pixel (u, v) at (v/2)*cstride + 2*(u/2), V behind it.
+inline size_t uv_elems(const vpcc_image_u16& a) {
+  if (a.width == 0 || a.height == 0) return 2;
+  return (size_t)((a.height - 1) / 2) * a.cstride + 2 * (size_t)((a.width - 1) / 2) + 2;
+}
+
 // ------------------------------------------------------------------------------------------------ memory of a gof
 constexpr int kGofParts = 2;          // the big blocks come in parts by frame: eight frames (one per XCD label) to part 0, the next
 inline int gof_part_of(uint32_t frame) { return (int)((frame >> 3) % kGofParts); }   // eight to part 1, ... (DESIGN.md 4.1 "Two homes")

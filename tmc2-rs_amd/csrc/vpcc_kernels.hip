@@ -510,6 +510,9 @@ __device__ __forceinline__ GenWork gen_work(uint32_t first, uint32_t count, uint
 #ifndef VPCC_GEN_WAVES
 #define VPCC_GEN_WAVES 7
 #endif
+// kLayout (both kernels of the general sequence): the launch's frames carry VPCC_FRAME_LAYOUT_MASK bits — shifted samples, maybe
+// interleaved chroma (uniform selections); false: the planar kernel as it always was.
+template <bool kLayout>
 __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPCC_GEN_WAVES, 8))) void k_general(const DevFrame* __restrict__ frames, uint32_t first, uint32_t count, uint32_t groups_per_frame, uint32_t interleave, uint32_t lanes, uint32_t gen) {
   const GenWork work = gen_work(first, count, groups_per_frame, interleave, lanes);
   if (!work.any) return;
@@ -554,7 +557,7 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
       patch_n[j] = b.patch;
       const uint32_t pv = log2R != 0xFFu ? i >> log2R : i / R, pu = i - pv * R;
       const uint32_t owner = gl(f.block_to_patch)[b.canvas_block];
-      const PixelOut o = eval_pixel(f, b, pu, pv);
+      const PixelOut o = eval_pixel<kLayout>(f, b, pu, pv);
       if (owner == (uint32_t)b.patch + 1u) {
         if (o.n) {
           pxy[j][0] = (uint32_t)o.p0.c[0] | ((uint32_t)o.p0.c[1] << 16);
@@ -599,8 +602,11 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
   // (the two layers written out, not a loop over a layer index: indexing the descriptor's arrays by a per-lane loop
   // counter made the compiler fetch their fields with scalar loads inside a waterfall loop, per unit and layer)
   uint32_t col[kU][2];
-  const uint16_t* const ay0 = f.attr_y[0]; const uint16_t* const au0 = f.attr_u[0]; const uint16_t* const av0 = f.attr_v[0];
-  const uint16_t* const ay1 = f.attr_y[1]; const uint16_t* const au1 = f.attr_u[1]; const uint16_t* const av1 = f.attr_v[1];
+  // Interleaved chroma (VPCC_FRAME_UV_INTERLEAVED: attr_v is null, never read): U at (y/2)*cstride + 2*(x/2) of attr_u, V behind it;
+  // planar: U and V at (y/2)*cstride + x/2 of their planes.  Samples >> the attribute shift (uniform; 0 for planar frames).
+  const uint32_t uvs = kLayout && layout_uv(f.layout) ? 1u : 0u, ash = kLayout ? layout_attr_shift(f.layout) : 0u;
+  const uint16_t* const ay0 = f.attr_y[0]; const uint16_t* const au0 = f.attr_u[0]; const uint16_t* const av0 = uvs ? f.attr_u[0] + 1 : f.attr_v[0];
+  const uint16_t* const ay1 = f.attr_y[1]; const uint16_t* const au1 = f.attr_u[1]; const uint16_t* const av1 = uvs ? f.attr_u[1] + 1 : f.attr_v[1];
   const uint32_t as0 = f.attr_stride[0], as1 = f.attr_stride[1], ac0 = f.attr_cstride[0], ac1 = f.attr_cstride[1];
   const bool has_attr = f.has_attr != 0;
 #pragma unroll
@@ -608,13 +614,13 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
     col[j][0] = col[j][1] = 0;
     const uint32_t np = patch_n[j] >> 16, x = cxy[j] & 0xFFFFu, y = cxy[j] >> 16;
     if (has_attr && np >= 1u) {
-      const uint32_t cidx = (y >> 1) * ac0 + (x >> 1);                                            // chroma nearest neighbour
-      const vpcc_color3 c = yuv10_to_rgb8_fast(gl(ay0)[y * as0 + x], gl(au0)[cidx], gl(av0)[cidx]);
+      const uint32_t cidx = (y >> 1) * ac0 + ((x >> 1) << uvs);                                   // chroma nearest neighbour
+      const vpcc_color3 c = yuv10_to_rgb8_fast(gl(ay0)[y * as0 + x] >> ash, gl(au0)[cidx] >> ash, gl(av0)[cidx] >> ash);
       col[j][0] = (uint32_t)c.r | ((uint32_t)c.g << 8) | ((uint32_t)c.b << 16);
     }
     if (has_attr && np == 2u) {
-      const uint32_t cidx = (y >> 1) * ac1 + (x >> 1);
-      const vpcc_color3 c = yuv10_to_rgb8_fast(gl(ay1)[y * as1 + x], gl(au1)[cidx], gl(av1)[cidx]);
+      const uint32_t cidx = (y >> 1) * ac1 + ((x >> 1) << uvs);
+      const vpcc_color3 c = yuv10_to_rgb8_fast(gl(ay1)[y * as1 + x] >> ash, gl(au1)[cidx] >> ash, gl(av1)[cidx] >> ash);
       col[j][1] = (uint32_t)c.r | ((uint32_t)c.g << 8) | ((uint32_t)c.b << 16);
     }
   }
@@ -702,6 +708,7 @@ __device__ unsigned long long g_gen_stamps[kGenStampSlots][16];
 #ifndef VPCC_GENB_WAVES
 #define VPCC_GENB_WAVES 8
 #endif
+template <bool kLayout>
 __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPCC_GENB_WAVES, 8))) void k_general_blocks(const DevFrame* __restrict__ frames, uint32_t first, uint32_t count, uint32_t groups_per_frame, uint32_t interleave, uint32_t lanes, uint32_t gen) {
   const GenWork work = gen_work(first, count, groups_per_frame, interleave, lanes);
   if (!work.any) return;
@@ -721,6 +728,10 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
   const uint32_t pu0 = tid & (f.R - 1u), pv0 = tid >> log2R;
   const ColourKeys keys = vpcc_colour_keys();
   const bool two = f.map_count > 1u, absolute = f.absolute_d1 != 0u, has_attr = f.has_attr != 0u;
+  // plane layout (uniform; all zero for planar frames): sample shifts, interleaved chroma (U at (y/2)*cstride + 2*(x/2) of attr_u,
+  // V the element behind it — attr_v is null and never read)
+  const uint32_t gsh = kLayout ? layout_geo_shift(f.layout) : 0u, ash = kLayout ? layout_attr_shift(f.layout) : 0u;
+  const uint32_t uvs = kLayout && layout_uv(f.layout) ? 1u : 0u;
   uint64_t* const state = reinterpret_cast<uint64_t*>(f.vb_count);          // one {generation | status | value} word per group
   // One group per workgroup, no loop: around a loop the compiler must assume that a register it is about to write may still be the
   // target of a load of the previous trip, and waits for ALL outstanding loads — in the middle of step 1b.
@@ -772,7 +783,7 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
     nn[j] = np[j] = 0;
     if (own[j]) {
       const bool mode0 = (b[j].axes_mode >> 6) == 0u;
-      const uint32_t pd1 = b[j].d1, d0 = s_d0[j] >> 2, d1 = s_d1[j] >> 2;                       // depth / 4, codec.rs:534
+      const uint32_t pd1 = b[j].d1, d0 = (s_d0[j] >> gsh) >> 2, d1 = (s_d1[j] >> gsh) >> 2;   // depth / 4, codec.rs:534
       const uint32_t n0 = (mode0 ? d0 + pd1 : (pd1 > d0 ? pd1 : d0) - d0) & 0xFFFFu;            // `as u16`
       uint32_t n1 = n0;
       if (two) n1 = (absolute ? (mode0 ? d1 + pd1 : (pd1 > d1 ? pd1 : d1) - d1) : (mode0 ? n0 + d1 : n0 - d1)) & 0xFFFFu;
@@ -818,7 +829,7 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
   uint32_t col[kU][2];
 #pragma unroll
   for (uint32_t l = 0; l < 2; ++l) {
-    const uint16_t* const ay = f.attr_y[l]; const uint16_t* const au = f.attr_u[l]; const uint16_t* const av = f.attr_v[l];
+    const uint16_t* const ay = f.attr_y[l]; const uint16_t* const au = f.attr_u[l]; const uint16_t* const av = uvs ? au + 1 : f.attr_v[l];
     const uint32_t as = f.attr_stride[l], ac = f.attr_cstride[l];
     uint32_t sy[kU], su[kU], sv[kU];
 #pragma unroll
@@ -826,7 +837,7 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
       sy[j] = su[j] = sv[j] = 0;
       if (has_attr && (before[j] >> 16) > l) {
         const uint32_t x = cxy[j] & 0xFFFFu, y = cxy[j] >> 16;
-        const uint32_t cidx = (__umul24(y >> 1, ac) + (x >> 1)) * 2u;                           // chroma nearest neighbour
+        const uint32_t cidx = (__umul24(y >> 1, ac) + ((x >> 1) << uvs)) * 2u;                  // chroma nearest neighbour
         sy[j] = ld32(ay, (__umul24(y, as) + x) * 2u);
         su[j] = ld32(au, cidx);
         sv[j] = ld32(av, cidx);
@@ -838,7 +849,7 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
     for (uint32_t j = 0; j < kU; ++j) {
       col[j][l] = 0;
       if (has_attr && (before[j] >> 16) > l) {
-        col[j][l] = yuv10_to_rgb8_packed(sy[j], su[j], sv[j], keys);
+        col[j][l] = yuv10_to_rgb8_packed(sy[j] >> ash, su[j] >> ash, sv[j] >> ash, keys);
       }
     }
     VPCC_GSTAMP(5 + l);
@@ -938,17 +949,24 @@ void launch_block_owner(const DevFrame* d_frames, uint32_t first, uint32_t count
   else
     hipLaunchKernelGGL(k_block_owner<64>, dim3((max_vb + 3) / 4, count), dim3(256), 0, (hipStream_t)stream, d_frames, first);
 }
-void launch_general(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_units, uint32_t gen, bool block_units, void* stream) {
+void launch_general(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_units, uint32_t gen, bool block_units,
+                    bool layout, void* stream) {
   if (!count || !max_units) return;
   if (block_units) {
     const uint32_t groups = (max_units + kGenBlockUnits - 1u) / kGenBlockUnits;
     const GenShape shape = gen_shape(count, groups, kGenInterleave);
-    hipLaunchKernelGGL(k_general_blocks, dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
+    if (layout)
+      hipLaunchKernelGGL((k_general_blocks<true>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
+    else
+      hipLaunchKernelGGL((k_general_blocks<false>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
     return;
   }
   const uint32_t groups = (max_units + kGenUnitsPerGroup - 1u) / kGenUnitsPerGroup;
   const GenShape shape = gen_shape(count, groups, kGenInterleave);
-  hipLaunchKernelGGL(k_general, dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
+  if (layout)
+    hipLaunchKernelGGL((k_general<true>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
+  else
+    hipLaunchKernelGGL((k_general<false>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
 }
 // Plane ingest by the GPU itself: every workgroup pulls 64-KB pieces of page-locked HOST memory over PCIe (zero-copy
 // reads, 16 B per lane, coalesced) and stores them in HBM.  One launch moves all planes of a gof: 57 GB/s with 64

@@ -290,18 +290,34 @@ __device__ __forceinline__ void load_geometry(CFrame& f, const Item& it, uint32_
 
 // Attribute samples; chroma is nearest-neighbour (src/decoder.rs:977): pixels 0,1 of the lane use
 // chroma sample px0/2, pixels 2,3 the next one.
+// kTileSurface (VPCC_FRAME_UV_INTERLEAVED, P010 / P016): those two chroma pairs lie side by side in the interleaved plane, at
+// element (py0/2)*cstride + px0 (px0 is a multiple of 4): ONE 8-byte load per layer, {U_a | V_a << 16, U_b | V_b << 16}, kept
+// as it came in s.u (low dword) and s.v (high dword) until emit_item splits it — the same bytes as the planar U and V loads.
+// attr_v is never read there (it is null).
+template <uint32_t kLayout>
 __device__ __forceinline__ void load_attributes(CFrame& f, const Item& it, uint32_t lane, Samples& s) {
   uint32_t px0, py0;
   load_origin(it, lane, s.occ, px0, py0);
-  // both layers come from one video: one row pitch (tile_planes_aligned), one offset per plane kind
-  const uint32_t c0 = (__umul24(py0 >> 1, f.attr_cstride[0]) + (px0 >> 1)) * 2u;
-  const uint32_t y0 = (__umul24(py0, f.attr_stride[0]) + px0) * 2u;
-  s.y0 = load4_row(f.attr_y[0], y0);   // absent planes alias present ones
-  s.u0 = load2(f.attr_u[0], c0);
-  s.v0 = load2(f.attr_v[0], c0);
-  s.y1 = load4_row(f.attr_y[1], y0);
-  s.u1 = load2(f.attr_u[1], c0);
-  s.v1 = load2(f.attr_v[1], c0);
+  if constexpr (kLayout == kTileSurface) {
+    const uint32_t c0 = (__umul24(py0 >> 1, f.attr_cstride[0]) + px0) * 2u;
+    const uint32_t y0 = (__umul24(py0, f.attr_stride[0]) + px0) * 2u;
+    s.y0 = load4_row(f.attr_y[0], y0);
+    const Px4 uv0 = load4_row(f.attr_u[0], c0);
+    s.y1 = load4_row(f.attr_y[1], y0);
+    const Px4 uv1 = load4_row(f.attr_u[1], c0);
+    s.u0 = uv0.lo; s.v0 = uv0.hi;
+    s.u1 = uv1.lo; s.v1 = uv1.hi;
+  } else {
+    // both layers come from one video: one row pitch (tile_planes_aligned), one offset per plane kind
+    const uint32_t c0 = (__umul24(py0 >> 1, f.attr_cstride[0]) + (px0 >> 1)) * 2u;
+    const uint32_t y0 = (__umul24(py0, f.attr_stride[0]) + px0) * 2u;
+    s.y0 = load4_row(f.attr_y[0], y0);   // absent planes alias present ones
+    s.u0 = load2(f.attr_u[0], c0);
+    s.v0 = load2(f.attr_v[0], c0);
+    s.y1 = load4_row(f.attr_y[1], y0);
+    s.u1 = load2(f.attr_u[1], c0);
+    s.v1 = load2(f.attr_v[1], c0);
+  }
 }
 
 // Which D1 points duplicate their D0 point (src/codec.rs:422-427), one bit per pixel of the lane.
@@ -319,6 +335,11 @@ __device__ __forceinline__ uint32_t pk_depth_min(uint32_t v, uint32_t dd) {
   a = __builtin_elementwise_min(a, __builtin_bit_cast(u16x2, dd));
   return __builtin_bit_cast(uint32_t, a);
 }
+// Both samples of a dword >> s (VPCC_FRAME_GEO_SHIFT / _ATTR_SHIFT): one v_pk_lshrrev_b16.
+__device__ __forceinline__ uint32_t pk_shr(uint32_t v, uint32_t s) {
+  return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, v) >> (u16x2)((uint16_t)s));
+}
+__device__ __forceinline__ Px4 pk_shr(const Px4& v, uint32_t s) { return Px4{pk_shr(v.lo, s), pk_shr(v.hi, s)}; }
 __device__ __forceinline__ uint32_t zero_halves(uint32_t x) {   // bit 0: low half zero, bit 1: high half zero
   return ((x & 0xFFFFu) ? 0u : 1u) | ((x >> 16) ? 0u : 2u);
 }
@@ -552,7 +573,7 @@ __device__ __forceinline__ void take_delivery(Samples& s) {
 // One item from samples in registers to its points in HBM: ranks, colours, compaction of the 8-B records
 // through the wave's LDS slots, then lane <-> point (back-projection, contiguous stores at `base`).
 // `n` = the item's point count (wave-uniform, from the count phase), `dup` its duplicate nibble.
-template <bool kStamps = false, class Hook>
+template <bool kStamps = false, uint32_t kLayout = kTilePlanar, class Hook>
 __device__ __forceinline__ void emit_item(CFrame& f, const Item& it, const Samples& cur, uint32_t dup, uint32_t n,
                                           uint32_t base, uint32_t lane, uint2* slots, uint32_t variant, Hook before_stores,
                                           unsigned long long* t_acc = nullptr) {
@@ -570,8 +591,21 @@ __device__ __forceinline__ void emit_item(CFrame& f, const Item& it, const Sampl
     pixel_ranks(it, cur, dup, cnt, lane, reinterpret_cast<unsigned char*>(slots), rk);
     uint32_t rgb0[4] = {0, 0, 0, 0}, rgb1[4] = {0, 0, 0, 0};
     if (f.has_attr && !(variant & 8u)) {
-      colours4(cur.y0, cur.u0, cur.v0, rgb0);
-      if (f.map_count > 1) colours4(cur.y1, cur.u1, cur.v1, rgb1);
+      if constexpr (kLayout == kTilePlanar) {
+        colours4(cur.y0, cur.u0, cur.v0, rgb0);
+        if (f.map_count > 1) colours4(cur.y1, cur.u1, cur.v1, rgb1);
+      } else {
+        // interleaved chroma: {U_a | V_a << 16, U_b | V_b << 16} (s.u, s.v as loaded) -> U_a | U_b << 16 and V_a | V_b << 16, two
+        // v_perm_b32 per layer; then every sample >> the attribute shift, two samples per instruction
+        const uint32_t as = layout_attr_shift(f.layout);
+        uint32_t u0 = cur.u0, v0 = cur.v0, u1 = cur.u1, v1 = cur.v1;
+        if constexpr (kLayout == kTileSurface) {
+          u0 = __builtin_amdgcn_perm(cur.v0, cur.u0, 0x05040100u); v0 = __builtin_amdgcn_perm(cur.v0, cur.u0, 0x07060302u);
+          u1 = __builtin_amdgcn_perm(cur.v1, cur.u1, 0x05040100u); v1 = __builtin_amdgcn_perm(cur.v1, cur.u1, 0x07060302u);
+        }
+        colours4(pk_shr(cur.y0, as), pk_shr(u0, as), pk_shr(v0, as), rgb0);
+        if (f.map_count > 1) colours4(pk_shr(cur.y1, as), pk_shr(u1, as), pk_shr(v1, as), rgb1);
+      }
     }
     // patch-local offsets of the lane's pixels: Default (du, dv) = (4q + j, r); Swap (du, dv) = (r, 4q + j)
     const uint32_t q4 = 4u * (lane & 3u), r = lane >> 2;
@@ -671,7 +705,9 @@ __device__ __forceinline__ void emit_item(CFrame& f, const Item& it, const Sampl
 // apart (measured: profiles/r02).
 __device__ __forceinline__ uint32_t item_in_group(uint32_t wave, uint32_t i) { return i * kTileWaves + wave; }
 
-template <bool kStamps>
+// kLayout (TileLayout, from the gof's frames): kTilePlanar is the kernel as it always was; the other two read shifted samples,
+// kTileSurface the interleaved chroma of P010 / P016 surfaces — the same bytes per lane, a few packed VALU operations more.
+template <bool kStamps, uint32_t kLayout>
 __global__ __launch_bounds__(64 * kTileWaves) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_recon_tiles(const DevFrame* __restrict__ frames, uint32_t first,
                                                      uint32_t count, uint32_t gen,
@@ -839,6 +875,11 @@ void k_recon_tiles(const DevFrame* __restrict__ frames, uint32_t first,
       read_early();
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
+        if constexpr (kLayout != kTilePlanar) {               // depth = (sample >> s) / 4 from here on: classify, put_records
+          const uint32_t gs = layout_geo_shift(f.layout);
+          s4[i].g0 = pk_shr(s4[i].g0, gs);
+          s4[i].g1 = pk_shr(s4[i].g1, gs);
+        }
         const uint32_t dup = classify(f, it4[i], s4[i]) & s4[i].occ;
         gn0[i] = s4[i].g0; gn1[i] = s4[i].g1;
         // classify() does not touch the samples on every path (single map, degenerate axes): make the
@@ -920,7 +961,7 @@ void k_recon_tiles(const DevFrame* __restrict__ frames, uint32_t first,
         nxt.occ = within ? (occ_cur >> (4u * (i + 1u))) & 0xFu : (have_next ? occ_next & 0xFu : cur.occ);
         nxt.g0 = within ? gc0[(i + 1u) & 3u] : gn0[0];                  // unrolled: static indices
         nxt.g1 = within ? gc1[(i + 1u) & 3u] : gn1[0];
-        if (!(variant & 256u)) load_attributes(fp, nit, lane, nxt);
+        if (!(variant & 256u)) load_attributes<kLayout>(fp, nit, lane, nxt);
         else { nxt.y0 = nxt.y1 = Px4{0u, 0u}; nxt.u0 = nxt.v0 = nxt.u1 = nxt.v1 = 0u; }
 
         __builtin_amdgcn_s_setprio(0);
@@ -928,7 +969,7 @@ void k_recon_tiles(const DevFrame* __restrict__ frames, uint32_t first,
           const uint32_t dup = (dup_cur >> (4u * i)) & 0xFu;                 // from the count phase
           // Take delivery of the prefetched samples before this item's stores are issued: waited for
           // later, the in-order vmcnt would make that wait cover the stores as well.
-          emit_item<kStamps>(f, it, cur, dup, n, base, lane, slots, variant, [&]() {
+          emit_item<kStamps, kLayout>(f, it, cur, dup, n, base, lane, slots, variant, [&]() {
             take_delivery(nxt);
             asm volatile("" : "+v"(t_ahead));
             if (i + 1u == K) {
@@ -958,7 +999,7 @@ void k_recon_tiles(const DevFrame* __restrict__ frames, uint32_t first,
       const Item nit = load_item(f.tiles + (next_item < f.n_tiles ? next_item : 0u));
       a_first.occ = occ_next & 0xFu;
       a_first.g0 = gn0[0]; a_first.g1 = gn1[0];
-      if (!(variant & 256u)) load_attributes(f, nit, lane, a_first);
+      if (!(variant & 256u)) load_attributes<kLayout>(f, nit, lane, a_first);
       take_delivery(a_first);                                // once per workgroup: keeps the item loop free of waits on `cur`
 #pragma unroll
       for (int j = 0; j < 4; ++j) { gc0[j] = gn0[j]; gc1[j] = gn1[j]; }
@@ -1013,7 +1054,7 @@ extern "C" int vpcc_debug_read_stamps(unsigned long long* out16, int reset) {
 namespace vpcc {
 
 void launch_tiles(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_groups, uint32_t gen,
-                  const TileLaunchMap& map, uint32_t resident_per_xcd, void* stream) {
+                  const TileLaunchMap& map, uint32_t resident_per_xcd, TileLayout layout, void* stream) {
   if (!count || !max_groups) return;
   // groups each workgroup is expected to pipeline (tickets are drawn dynamically; this only sizes the grid)
   uint32_t depth = 3, variant = 0;
@@ -1037,14 +1078,22 @@ void launch_tiles(const DevFrame* d_frames, uint32_t first, uint32_t count, uint
     grid = 8u * std::max(kFramesInFlight,                     // of frames needs a workgroup, however small the device
                          std::min(resident_per_xcd * 4u / kTileWaves, kFramesInFlight * wgs));
 #ifdef VPCC_DIAGNOSTIC
-  if (variant & 64u) {
-    hipLaunchKernelGGL(k_recon_tiles<true>, dim3(grid), dim3(64 * kTileWaves), 0, (hipStream_t)stream, d_frames, first, count,
-                       gen, variant, map);
+  if ((variant & 64u) && layout == kTilePlanar) {
+    hipLaunchKernelGGL((k_recon_tiles<true, kTilePlanar>), dim3(grid), dim3(64 * kTileWaves), 0, (hipStream_t)stream, d_frames, first,
+                       count, gen, variant, map);
     return;
   }
 #endif
-  hipLaunchKernelGGL(k_recon_tiles<false>, dim3(grid), dim3(64 * kTileWaves), 0, (hipStream_t)stream, d_frames, first, count,
-                     gen, variant, map);
+  // one instantiation per plane layout of the gof (all its frames share one: vpcc_gof_create)
+  if (layout == kTileSurface)
+    hipLaunchKernelGGL((k_recon_tiles<false, kTileSurface>), dim3(grid), dim3(64 * kTileWaves), 0, (hipStream_t)stream, d_frames,
+                       first, count, gen, variant, map);
+  else if (layout == kTileShifted)
+    hipLaunchKernelGGL((k_recon_tiles<false, kTileShifted>), dim3(grid), dim3(64 * kTileWaves), 0, (hipStream_t)stream, d_frames,
+                       first, count, gen, variant, map);
+  else
+    hipLaunchKernelGGL((k_recon_tiles<false, kTilePlanar>), dim3(grid), dim3(64 * kTileWaves), 0, (hipStream_t)stream, d_frames,
+                       first, count, gen, variant, map);
 }
 
 __global__ void k_warm_tiles() {}

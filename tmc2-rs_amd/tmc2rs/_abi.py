@@ -40,6 +40,21 @@ VPCC_GOF_PROFILE = 0x4
 VPCC_GOF_ASYNC_UPLOAD = 0x8
 VPCC_GOF_COPY_PLANES = 0x20
 
+# vpcc_frame_desc.flags: planes of a hardware decoder (P010 / P016 surfaces)
+VPCC_FRAME_UV_INTERLEAVED = 0x2
+
+
+def VPCC_FRAME_GEO_SHIFT(s):
+    return int(s) << 8
+
+
+def VPCC_FRAME_ATTR_SHIFT(s):
+    return int(s) << 12
+
+
+VPCC_VIDEO_YUV420P10LE = 0
+VPCC_VIDEO_P010LE = 1
+
 VPCC_VERIFY_INGEST = 0x1
 VPCC_VERIFY_RECONSTRUCT = 0x2
 VPCC_VERIFY_DELIVERY = 0x4
@@ -131,7 +146,10 @@ def _plane(a, dtype):
 
 def host_frame_desc(frame):
     """Builds a FrameDesc over the numpy arrays of a synthetic/ingested frame
-    dict (see synth.make_frame).  Returns (desc, keepalive)."""
+    dict (see synth.make_frame).  Returns (desc, keepalive).
+    An attribute map given as a 2-tuple (Y, UV) is a semi-planar surface (synth.to_semiplanar): one interleaved
+    U,V plane, VPCC_FRAME_UV_INTERLEAVED and v = NULL.  "geo_shift" / "attr_shift" set VPCC_FRAME_GEO_SHIFT /
+    VPCC_FRAME_ATTR_SHIFT; "flags" is OR-ed in as given."""
     d = FrameDesc()
     d.width, d.height = int(frame["width"]), int(frame["height"])
     d.occupancy_resolution = int(frame["occupancy_resolution"])
@@ -139,7 +157,8 @@ def host_frame_desc(frame):
     d.map_count = int(frame.get("map_count", 2))
     d.absolute_d1 = int(frame.get("absolute_d1", 1))
     d.attribute_count = int(frame.get("attribute_count", 1))
-    d.flags = int(frame.get("flags", 0))
+    d.flags = int(frame.get("flags", 0)) | VPCC_FRAME_GEO_SHIFT(frame.get("geo_shift", 0)) | \
+        VPCC_FRAME_ATTR_SHIFT(frame.get("attr_shift", 0))
     keep = []
     occ, d.occupancy.y, d.occupancy.width, d.occupancy.height, d.occupancy.stride = _plane(frame["occupancy"], np.uint8)
     keep.append(occ)
@@ -154,6 +173,12 @@ def host_frame_desc(frame):
         if a is not None:
             A = d.attribute[m]
             y, A.y, A.width, A.height, A.stride = _plane(a[0], np.uint16)
+            if len(a) == 2:                          # (Y, UV): interleaved chroma, v = NULL
+                uv, A.u, _, _, A.cstride = _plane(a[1], np.uint16)
+                A.v = None
+                d.flags |= VPCC_FRAME_UV_INTERLEAVED
+                keep += [y, uv]
+                continue
             u, A.u, _, _, A.cstride = _plane(a[1], np.uint16)
             v, A.v, _, _, cs2 = _plane(a[2], np.uint16)
             assert cs2 == A.cstride, "U and V planes must share one stride"
@@ -274,6 +299,7 @@ def load_library():
     lib.vpcc_gof_output_digests.argtypes = [vp, u32, u32, vp]
     lib.vpcc_gof_plane_digests.argtypes = [vp, u32, u32, vp]
     lib.vpcc_decoder_set_verify.argtypes = [vp, u32]
+    lib.vpcc_decoder_set_video_format.argtypes = [vp, C.c_int]
     lib.vpcc_decoder_frame_digest.argtypes = [vp, C.POINTER(u64)]
     lib.vpcc_decoder_verify_stats.argtypes = [vp, C.POINTER(VerifyStats)]
     lib.vpcc_decoder_close.restype = None

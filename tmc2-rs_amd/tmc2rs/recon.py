@@ -58,6 +58,72 @@ def digest_planes(frame):
     return out.value
 
 
+def _root(a):
+    """The numpy buffer that owns a plane's memory (a strided view's base)."""
+    while isinstance(a.base, np.ndarray):
+        a = a.base
+    return a
+
+
+class DeviceFrame:
+    """A frame dict's planes in device memory as they lie on the host — each buffer that holds planes (a semi-planar surface of
+    synth.to_semiplanar with its pitch, padding and luma / UV arrangement, or a tight planar plane) becomes ONE device
+    allocation of the same bytes — and `desc`, a FrameDesc over the device copies for VPCC_MEM_DEVICE (borrowed planes; the patch
+    table stays on the host, where vpcc_gof_create reads it).  torch is only the allocator and the copy engine here."""
+
+    def __init__(self, frame, device=0):
+        import torch
+        self.dev = torch.device(f"cuda:{device}")
+        self.desc, self._host_keep = host_frame_desc(frame)
+        self._roots = self._roots_of(self._host_keep[:-1])             # (the last kept array is the patch table)
+        self.buffers = [torch.from_numpy(r.view(np.uint8).reshape(-1)).to(self.dev) for r in self._roots]
+        torch.cuda.synchronize(self.dev)
+        d = self.desc
+
+        def remap(ptr):
+            for r, t in zip(self._roots, self.buffers):
+                lo = r.ctypes.data
+                if lo <= ptr < lo + r.nbytes:
+                    return t.data_ptr() + (ptr - lo)
+            raise ValueError("a plane outside the frame's buffers")
+        d.occupancy.y = remap(d.occupancy.y)
+        for m in range(2):
+            for img in (d.geometry[m], d.attribute[m]):
+                for name in ("y", "u", "v"):
+                    if getattr(img, name):
+                        setattr(img, name, remap(getattr(img, name)))
+
+    @staticmethod
+    def _roots_of(arrays):
+        roots = []
+        for a in arrays:
+            r = _root(a)
+            if not r.flags["C_CONTIGUOUS"]:
+                raise ValueError("plane buffers must be contiguous")
+            if not any(r is q for q in roots):
+                roots.append(r)
+        return roots
+
+    def stage(self, frame):
+        """Device copies of another frame of the same layout (same buffers, sizes and plane offsets), for fill()."""
+        desc, keep = host_frame_desc(frame)
+        roots = self._roots_of(keep[:-1])
+        assert [r.nbytes for r in roots] == [r.nbytes for r in self._roots], "another layout"
+        return [t.to(self.dev) for t in (self._torch_bytes(r) for r in roots)]
+
+    @staticmethod
+    def _torch_bytes(r):
+        import torch
+        return torch.from_numpy(r.view(np.uint8).reshape(-1))
+
+    def fill(self, staged, stream=None):
+        """Refills the device buffers from stage()d copies, enqueued on `stream` (a torch stream; None: the current one)."""
+        import torch
+        with torch.cuda.stream(stream) if stream is not None else torch.cuda.device(self.dev):
+            for t, src in zip(self.buffers, staged):
+                t.copy_(src, non_blocking=True)
+
+
 def verify_flags(verify):
     """Decoder(verify=...): None / 0 (off), an int of VPCC_VERIFY_* bits, or a string "ingest,reconstruct,delivery" / "all"."""
     if not verify:
@@ -317,10 +383,12 @@ class Decoder:
     Iterator, src/lib.rs:70-154).  Iterating yields dicts {n, xyz, rgb} in presentation order."""
 
     def __init__(self, path, devices=(0,), occupancy_yuv=None, geometry_yuv=None, attribute_yuv=None,
-                 occupancy_precision=4, verify=None):
+                 occupancy_precision=4, verify=None, video_format=None):
         """`path`: a .vpccgof container, or — with the raw decoded videos given — a V3C sample stream (.bin).
         `verify`: the verified mode (vpcc_decoder_set_verify) — "ingest,reconstruct,delivery", "all" or VPCC_VERIFY_* bits;
-        None leaves it to the environment (VPCC_DECODER_VERIFY)."""
+        None leaves it to the environment (VPCC_DECODER_VERIFY).
+        `video_format`: layout of the raw geometry / attribute files (vpcc_decoder_set_video_format) — "yuv420p10le" (the default)
+        or "p010le" (a hardware decoder's semi-planar output)."""
         self.lib = _abi.load_library()
         self.h = C.c_void_p()
         dev = (C.c_int * len(devices))(*devices)
@@ -332,6 +400,11 @@ class Decoder:
                                                 occupancy_precision, dev, len(devices), C.byref(self.h))
         if st:
             raise VpccError(st, "vpcc_decoder_open")
+        if video_format is not None:
+            fmt = {"yuv420p10le": _abi.VPCC_VIDEO_YUV420P10LE, "p010le": _abi.VPCC_VIDEO_P010LE}.get(video_format, video_format)
+            st = self.lib.vpcc_decoder_set_video_format(self.h, int(fmt))
+            if st:
+                raise VpccError(st, "vpcc_decoder_set_video_format", self.error())
         if verify is not None:
             st = self.lib.vpcc_decoder_set_verify(self.h, verify_flags(verify))
             if st:

@@ -219,3 +219,112 @@ def small_frame(index, width=64, height=64, precision=4, resolution=16, **kw):
     kw.setdefault("cover_target", 0.8)
     kw.setdefault("overlap_prob", 0.4)
     return make_frame(width, height, precision, resolution, seed=0x51A11000 + index, coord_bits=10, **kw)
+
+
+# ------------------------------------------------------------------ semi-planar surfaces (P010 / P016)
+def _surface_buffer(rows, pitch_elems, fill_seed):
+    """A u16 buffer of `rows` rows of `pitch_elems` elements, filled with noise: padding that must never be read."""
+    return (rand_u64(fill_seed, 90, rows * pitch_elems) & np.uint64(0xFFFF)).astype(np.uint16).reshape(rows, pitch_elems)
+
+
+def _msb(values, shift, junk_seed, stream):
+    """(value << shift) | junk in u16 (junk: random low bits below `shift`, or 0)."""
+    v = (np.asarray(values).astype(np.uint32) << np.uint32(shift)) & np.uint32(0xFFFF)
+    if junk_seed is not None and shift:
+        j = rand_u64(junk_seed, stream, v.size) & np.uint64((1 << shift) - 1)
+        v = v | j.astype(np.uint32).reshape(v.shape)
+    return v.astype(np.uint16)
+
+
+def to_semiplanar(frame, shift=6, junk_seed=None, pitch_align=256, geo_shift=None, attr_shift=None, extra_pitch=0,
+                  uv_separate=False):
+    """The same frame as a hardware decoder's P010 / P016 surfaces (include/vpcc_recon.h, VPCC_FRAME_UV_INTERLEAVED):
+    every geometry and attribute sample MSB-aligned — (value << s) | junk, s = geo_shift / attr_shift (default `shift`), junk
+    random low bits when `junk_seed` is given, else 0 —, the attribute chroma one interleaved U,V plane per map.
+    The frame's flags gain VPCC_FRAME_UV_INTERLEAVED (whether or not it has attributes: all frames of a gof share a layout).
+    Rows have a pitch of 2 * width bytes rounded up to `pitch_align` (+ `extra_pitch` bytes); an attribute surface holds its
+    luma rows, a gap, then its UV rows in one buffer, as a decoder's frame pool lays them out (`uv_separate`: the UV plane in an
+    allocation of its own).  Padding holds noise.  Attribute maps become (Y, UV) 2-tuples; occupancy stays as it is (the luma
+    of an NV12 surface).  from_semiplanar gives back the planar frame the samples stand for."""
+    gs = shift if geo_shift is None else geo_shift
+    ash = shift if attr_shift is None else attr_shift
+    W, H = int(frame["width"]), int(frame["height"])
+    out = dict(frame)
+    seed = int(frame.get("seed", 0)) & 0xFFFFFFFF
+
+    def pitch_of(width):
+        b = -(-2 * width // pitch_align) * pitch_align + extra_pitch
+        assert b % 2 == 0
+        return b // 2
+
+    geo = []
+    for m, g in enumerate(frame["geometry"]):
+        g = np.asarray(g)
+        p = pitch_of(g.shape[1])
+        buf = _surface_buffer(g.shape[0], p, seed + 17 * m)
+        buf[:, :g.shape[1]] = _msb(g, gs, junk_seed, 40 + m)
+        geo.append(buf[:, :g.shape[1]])
+    out["geometry"] = geo
+    attr = []
+    for m, (y, u, v) in enumerate(frame["attribute"]):
+        y, u, v = np.asarray(y), np.asarray(u), np.asarray(v)
+        h, w = y.shape
+        ch, cw = u.shape
+        p = pitch_of(max(w, 2 * cw))
+        gap = 4                                                       # rows between luma and chroma: never adjacent
+        if uv_separate:
+            ybuf = _surface_buffer(h, p, seed + 101 + m)
+            cbuf = _surface_buffer(ch, p, seed + 201 + m)
+        else:
+            whole = _surface_buffer(h + gap + ch, p, seed + 101 + m)
+            ybuf, cbuf = whole[:h], whole[h + gap:]
+        ybuf[:, :w] = _msb(y, ash, junk_seed, 50 + m)
+        cbuf[:, 0:2 * cw:2] = _msb(u, ash, junk_seed, 60 + m)
+        cbuf[:, 1:2 * cw:2] = _msb(v, ash, junk_seed, 70 + m)
+        attr.append((ybuf[:, :w], cbuf[:, :2 * cw]))
+    out["attribute"] = attr
+    out["geo_shift"], out["attr_shift"] = gs, ash
+    out["flags"] = int(frame.get("flags", 0)) | 0x2          # VPCC_FRAME_UV_INTERLEAVED, also without attributes: one gof, one layout
+    return out
+
+
+def from_semiplanar(frame):
+    """The planar frame (tight yuv420p10le-style planes, no shifts) whose samples a semi-planar frame stands for: every sample
+    >> its shift, the chroma de-interleaved — what the oracle reconstructs."""
+    gs, ash = int(frame.get("geo_shift", 0)), int(frame.get("attr_shift", 0))
+    out = {k: v for k, v in frame.items() if k not in ("geo_shift", "attr_shift")}
+    out["geometry"] = [np.ascontiguousarray(np.asarray(g) >> np.uint16(gs)) for g in frame["geometry"]]
+    attr = []
+    for a in frame["attribute"]:
+        if len(a) == 2:
+            y, uv = np.asarray(a[0]), np.asarray(a[1])
+            attr.append((np.ascontiguousarray(y >> np.uint16(ash)), np.ascontiguousarray(uv[:, 0::2] >> np.uint16(ash)),
+                         np.ascontiguousarray(uv[:, 1::2] >> np.uint16(ash))))
+        else:
+            attr.append(tuple(np.ascontiguousarray(np.asarray(p) >> np.uint16(ash)) for p in a))
+    out["attribute"] = attr
+    out["flags"] = int(frame.get("flags", 0)) & ~0xFF02
+    return out
+
+
+def p010_bytes(y, u, v, junk_seed=None, stream=0):
+    """One P010LE frame: the W x H luma, then H/2 rows of W interleaved U,V samples, 10 bits in [15:6], little endian."""
+    y, u, v = np.asarray(y), np.asarray(u), np.asarray(v)
+    uv = np.zeros((u.shape[0], 2 * u.shape[1]), np.uint16)
+    uv[:, 0::2] = _msb(u, 6, junk_seed, 80 + 3 * stream)
+    uv[:, 1::2] = _msb(v, 6, junk_seed, 81 + 3 * stream)
+    return _msb(y, 6, junk_seed, 82 + 3 * stream).astype("<u2").tobytes() + uv.astype("<u2").tobytes()
+
+
+def yuv420p10le_to_p010le(src, dst, width, height, junk_seed=None):
+    """Rewrites a raw yuv420p10le file (frames back to back, as vpcc_decoder_open_v3c reads them) as P010LE, frame by frame."""
+    W, H = int(width), int(height)
+    luma, chroma = W * H, (W // 2) * (H // 2)
+    data = np.fromfile(str(src), dtype="<u2")
+    per = luma + 2 * chroma
+    assert data.size % per == 0, "not a whole number of frames"
+    with open(str(dst), "wb") as o:
+        for k in range(data.size // per):
+            f = data[k * per:(k + 1) * per]
+            o.write(p010_bytes(f[:luma].reshape(H, W), f[luma:luma + chroma].reshape(H // 2, W // 2),
+                               f[luma + chroma:].reshape(H // 2, W // 2), junk_seed, stream=k))

@@ -1102,7 +1102,8 @@ extern "C" int vpcc_debug_read_stamps(unsigned long long* out16, int reset) {
 namespace vpcc {
 
 void launch_tiles(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_groups, uint32_t gen,
-                  const TileLaunchMap& map, uint32_t resident_per_xcd, void* stream) {
+                  const TileLaunchMap& map, uint32_t resident_per_xcd, TileLayout layout, void* stream) {
+  (void)layout;                        // always kTilePlanar: the build's tile_planes_aligned sends other layouts to the general sequence
   if (!count || !max_groups) return;
   // groups each workgroup is expected to pipeline (tickets are drawn dynamically; this only sizes the grid)
   uint32_t depth = 3, variant = 0;
