@@ -244,7 +244,11 @@ int  vpcc_host_free(vpcc_ctx* ctx, void* ptr);   /* ctx may be NULL once the con
 
 /* Validates a frame descriptor on the host exactly as far as the reference's
  * asserts would fire while walking it (patch extents, plane sizes, supported
- * envelope).  Pure host function, no GPU needed. */
+ * envelope).  Pure host function, no GPU needed.
+ * Beyond the reference: VPCC_ERR_UNSUPPORTED for a frame whose general-sequence
+ * unit count — sum of size_u0 * size_v0 over the patches, times
+ * ceil(R * R / 256) for R >= 16 — exceeds 2^31 (R = 32: 2^29 virtual blocks;
+ * R = 16 frames never reach it). */
 int  vpcc_frame_validate(const vpcc_frame_desc* frame);
 
 /* Upper bound on the number of points one frame can produce

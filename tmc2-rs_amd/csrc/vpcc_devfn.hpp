@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "vpcc_colour.h"
 #include "vpcc_device.hpp"
 
@@ -164,7 +166,9 @@ struct PixelOut {
 };
 
 // kLayout: the frame has VPCC_FRAME_LAYOUT_MASK bits (the sample shifts are read from it; false: planar, no shifts)
-template <bool kLayout>
+// kWide: element indices into the planes in 64 bits (a borrowed plane whose row * stride + column reaches 2^32:
+// general_wide_planes); false: 32-bit indices, the kernel as it always was
+template <bool kLayout, bool kWide = false>
 __device__ __forceinline__ PixelOut eval_pixel(const DevFrame& f, const VBlock& b, uint32_t pu, uint32_t pv) {
   PixelOut o;
   o.n = 0;
@@ -180,10 +184,11 @@ __device__ __forceinline__ PixelOut eval_pixel(const DevFrame& f, const VBlock& 
   // Occupancy and both depths are requested TOGETHER (the pixel lies inside the canvas and the planes cover it: validate_frame),
   // and the pixel's points are built without a branch: with the depths behind `if (occ == 0) return` every occupied pixel paid
   // two dependent round trips to memory, one per plane kind.
-  const uint8_t occ = gl(f.occ)[oy * f.occ_stride + ox];                             // src/codec.rs:288-301, 393
+  typedef typename std::conditional<kWide, uint64_t, uint32_t>::type Index;
+  const uint8_t occ = gl(f.occ)[(Index)oy * f.occ_stride + ox];                      // src/codec.rs:288-301, 393
   const uint32_t gs = kLayout ? layout_geo_shift(f.layout) : 0u;                  // VPCC_FRAME_GEO_SHIFT
-  const uint32_t d0 = (uint32_t)(gl(f.geo[0])[o.y * f.geo_stride[0] + o.x] >> gs) >> 2;  // depth / 4, codec.rs:534
-  const uint32_t d1 = (uint32_t)(gl(f.geo[1])[o.y * f.geo_stride[1] + o.x] >> gs) >> 2;  // (one map: the descriptor's alias of layer 0)
+  const uint32_t d0 = (uint32_t)(gl(f.geo[0])[(Index)o.y * f.geo_stride[0] + o.x] >> gs) >> 2;  // depth / 4, codec.rs:534
+  const uint32_t d1 = (uint32_t)(gl(f.geo[1])[(Index)o.y * f.geo_stride[1] + o.x] >> gs) >> 2;  // (one map: the descriptor's alias of layer 0)
   o.p0 = make_point(b, pu, pv, d0);
   o.p1 = o.p0;
   uint32_t n = 1;

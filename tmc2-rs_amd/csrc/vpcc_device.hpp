@@ -291,12 +291,15 @@ constexpr uint32_t kGenBlockUnits = VPCC_GENB_UNITS;     // ... and of k_general
 #define VPCC_GENB_STAGE 2
 #endif
 constexpr uint32_t kGenBlockStage = VPCC_GENB_STAGE;     // units of a group that pass through the LDS together on their way out
-VPCC_HD inline uint32_t general_units(uint32_t R, uint32_t n_vblocks) {
+// (64 bits: at R > 16 the count outgrows the virtual blocks.  validate_frame refuses a frame above kGeneralMaxUnits, so that the
+// kernels' 32-bit unit and group arithmetic, the + kU - 1 roundings included, never wraps.)
+VPCC_HD inline uint64_t general_units(uint32_t R, uint32_t n_vblocks) {
   const uint64_t RR = (uint64_t)R * R;
-  if (RR >= 256u) return (uint32_t)(n_vblocks * ((RR + 255u) / 256u));
+  if (RR >= 256u) return n_vblocks * ((RR + 255u) / 256u);
   const uint32_t per = (uint32_t)(256u / RR);
-  return (n_vblocks + per - 1u) / per;
+  return ((uint64_t)n_vblocks + per - 1u) / per;
 }
+constexpr uint64_t kGeneralMaxUnits = 1ull << 31;
 // Which (frame of the launch, group) workgroup L of the pass takes, and how many workgroups a launch has: of `lanes` lanes — the eight
 // XCDs (workgroup L runs on XCD L % 8) for launches of eight frames or more, else one per frame — lane x takes frames x, x + lanes, ...,
 // `interleave` of them at a time with their groups in turn (why: vpcc_kernels.hip).  What the look-back relies on: every (frame,
@@ -318,14 +321,18 @@ inline GenShape gen_shape(uint32_t count, uint32_t groups_per_frame, uint32_t ma
   s.lanes = count >= 8u ? 8u : (count ? count : 1u);
   const uint32_t per_lane = (count + s.lanes - 1u) / s.lanes;
   s.interleave = per_lane < max_interleave ? (per_lane ? per_lane : 1u) : max_interleave;
-  s.grid = s.lanes * ((per_lane + s.interleave - 1u) / s.interleave) * s.interleave * groups_per_frame;
+  const uint64_t grid = (uint64_t)s.lanes * ((per_lane + s.interleave - 1u) / s.interleave) * s.interleave * groups_per_frame;
+  s.grid = grid < 0xFFFFFFFFull ? (uint32_t)grid : 0xFFFFFFFFu;   // (saturated: launch_general refuses a grid this large)
   return s;
 }
 // block_units: every frame of the launch has FrameShape::block_units (vpcc_host.hpp) — k_general_blocks, whose units are chunks
 // of ONE virtual block each, so that everything a block decides is scalar work; else k_general, which takes any frame.
 // layout: the frames carry VPCC_FRAME_LAYOUT_MASK bits (shifted samples, interleaved chroma): the kernels' instantiation that reads them.
-void launch_general(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_units, uint32_t gen, bool block_units,
-                    bool layout, void* stream);
+// wide: a frame of the launch has a plane whose largest element index reaches 2^32 (general_wide_planes; never with block_units):
+// the k_general instantiation with 64-bit plane indices.  false: nothing launched — the launch needs more threads than one grid
+// holds (2^32).
+bool launch_general(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_units, uint32_t gen, bool block_units,
+                    bool layout, bool wide, void* stream);
 // Where the workgroups of one tile-kernel launch start (kernel argument, by value).  A workgroup stays with its
 // frame; frames differ in size (S-longdress +-5 %, S-owlii +-11 % between the largest frame and the mean), so the
 // resident workgroups of an XCD are shared out among its frames in proportion to their tile counts instead of

@@ -136,11 +136,13 @@ extern "C" int vpcc_gof_reconstruct(vpcc_gof* g, uint32_t first, uint32_t count,
   if (b2p_len) HIP_TRY(ctx, hipMemsetAsync(g->d_b2p + g->b2p_off[first], 0, b2p_len * sizeof(uint32_t), s));
   uint32_t max_vb = 0, max_units = 0, max_samples = 0;
   bool block_units = getenv("VPCC_GENERAL_ANY_FRAME") == nullptr;       // (tests: k_general on frames k_general_blocks would take)
+  bool wide = false;
   for (uint32_t i = first; i < first + count; ++i) {
     const DevFrame& D = g->h_frames[i];
     block_units = block_units && g->shapes[i].block_units;
+    wide = wide || general_wide_planes(D);
     max_vb = std::max(max_vb, D.n_vblocks);
-    max_units = std::max(max_units, general_units(D.R, D.n_vblocks));
+    max_units = std::max(max_units, (uint32_t)general_units(D.R, D.n_vblocks));   // (<= kGeneralMaxUnits: validate_frame)
     const uint32_t side = (D.R + D.prec - 1u) / D.prec + 1u; // samples under R pixels that start anywhere: at most ceil(R / precision) + 1
     max_samples = std::max(max_samples, side * side);
   }
@@ -149,8 +151,9 @@ extern "C" int vpcc_gof_reconstruct(vpcc_gof* g, uint32_t first, uint32_t count,
   launch_block_owner(g->d_frames, first, count, max_vb, max_samples, s);
   T.end();
   T.begin(block_units ? "k_general_blocks" : "k_general");
-  launch_general(g->d_frames, first, count, max_units, g->generation, block_units, g->h_frames[first].layout != 0, s);
+  const bool launched = launch_general(g->d_frames, first, count, max_units, g->generation, block_units, g->h_frames[first].layout != 0, wide, s);
   T.end();
+  if (!launched) return fail(ctx, VPCC_ERR_UNSUPPORTED, "general sequence: more workgroups than one grid holds (launch fewer frames)");
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(g->results_ready, s));
   g->launched = true;

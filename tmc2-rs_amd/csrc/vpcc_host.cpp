@@ -116,6 +116,8 @@ int validate_frame(const vpcc_frame_desc* f, FrameShape* shape) {
     n_vb += (uint64_t)p.size_u0 * p.size_v0;
   }
   if (n_vb > 0x7FFFFFFFull) return VPCC_ERR_INVALID_ARG;
+  // the general sequence's units (either kernel's: general_units) must stay within what its 32-bit arithmetic handles
+  if (general_units((uint32_t)R, (uint32_t)n_vb) > kGeneralMaxUnits) return VPCC_ERR_UNSUPPORTED;
   if (shape) {
     shape->bw = (uint32_t)bw;
     shape->bh = (uint32_t)bh;
@@ -424,6 +426,20 @@ bool tile_planes_aligned(const DevFrame& d) {
     }
   }
   return true;
+}
+
+bool general_wide_planes(const DevFrame& d) {
+  const uint64_t lim = 1ull << 32, H = d.height, W = d.width;
+  if (!H || !W) return false;
+  if ((H - 1) / d.prec * d.occ_stride + (W - 1) / d.prec >= lim) return true;
+  const uint32_t uvs = layout_uv(d.layout) ? 1u : 0u;
+  for (uint32_t m = 0; m < d.map_count; ++m) {
+    if ((H - 1) * d.geo_stride[m] + (W - 1) >= lim) return true;
+    if (d.has_attr && ((H - 1) * d.attr_stride[m] + (W - 1) >= lim ||
+                       ((H - 1) >> 1) * d.attr_cstride[m] + (((W - 1) >> 1) << uvs) >= lim))
+      return true;
+  }
+  return false;
 }
 
 // Largest-remainder shares of `resident_per_xcd` workgroups among the frames of each XCD label, at most

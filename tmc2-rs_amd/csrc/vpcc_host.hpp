@@ -160,5 +160,9 @@ struct PoolExtents {
 // Alignment preconditions of the tile kernel's vector loads for the planes as the kernels will see
 // them (device pointers and strides): 8-B aligned luma rows, 4-B aligned chroma pairs.
 bool tile_planes_aligned(const DevFrame& d);
+// Does the largest element index that k_general forms into one of the frame's planes — row * stride + column, chroma
+// (row / 2) * cstride + column / 2 (x 2 interleaved) — reach 2^32?  Only borrowed planes can (copied and host planes are
+// tight, with indices below 2^30); such a frame needs the k_general instantiation with 64-bit indices.
+bool general_wide_planes(const DevFrame& d);
 
 }  // namespace vpcc

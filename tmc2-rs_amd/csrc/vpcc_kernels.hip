@@ -512,7 +512,9 @@ __device__ __forceinline__ GenWork gen_work(uint32_t first, uint32_t count, uint
 #endif
 // kLayout (both kernels of the general sequence): the launch's frames carry VPCC_FRAME_LAYOUT_MASK bits — shifted samples, maybe
 // interleaved chroma (uniform selections); false: the planar kernel as it always was.
-template <bool kLayout>
+// kWide (k_general only): 64-bit element indices into the planes, for launches with a borrowed plane whose largest index read
+// reaches 2^32 (general_wide_planes); false: 32-bit indices, the kernel as it always was.
+template <bool kLayout, bool kWide = false>
 __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPCC_GEN_WAVES, 8))) void k_general(const DevFrame* __restrict__ frames, uint32_t first, uint32_t count, uint32_t groups_per_frame, uint32_t interleave, uint32_t lanes, uint32_t gen) {
   const GenWork work = gen_work(first, count, groups_per_frame, interleave, lanes);
   if (!work.any) return;
@@ -557,7 +559,7 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
       patch_n[j] = b.patch;
       const uint32_t pv = log2R != 0xFFu ? i >> log2R : i / R, pu = i - pv * R;
       const uint32_t owner = gl(f.block_to_patch)[b.canvas_block];
-      const PixelOut o = eval_pixel<kLayout>(f, b, pu, pv);
+      const PixelOut o = eval_pixel<kLayout, kWide>(f, b, pu, pv);
       if (owner == (uint32_t)b.patch + 1u) {
         if (o.n) {
           pxy[j][0] = (uint32_t)o.p0.c[0] | ((uint32_t)o.p0.c[1] << 16);
@@ -609,18 +611,19 @@ __global__ __launch_bounds__(kGenThreads) __attribute__((amdgpu_waves_per_eu(VPC
   const uint16_t* const ay1 = f.attr_y[1]; const uint16_t* const au1 = f.attr_u[1]; const uint16_t* const av1 = uvs ? f.attr_u[1] + 1 : f.attr_v[1];
   const uint32_t as0 = f.attr_stride[0], as1 = f.attr_stride[1], ac0 = f.attr_cstride[0], ac1 = f.attr_cstride[1];
   const bool has_attr = f.has_attr != 0;
+  typedef typename std::conditional<kWide, uint64_t, uint32_t>::type Index;
 #pragma unroll
   for (uint32_t j = 0; j < kU; ++j) {
     col[j][0] = col[j][1] = 0;
     const uint32_t np = patch_n[j] >> 16, x = cxy[j] & 0xFFFFu, y = cxy[j] >> 16;
     if (has_attr && np >= 1u) {
-      const uint32_t cidx = (y >> 1) * ac0 + ((x >> 1) << uvs);                                   // chroma nearest neighbour
-      const vpcc_color3 c = yuv10_to_rgb8_fast(gl(ay0)[y * as0 + x] >> ash, gl(au0)[cidx] >> ash, gl(av0)[cidx] >> ash);
+      const Index cidx = (Index)(y >> 1) * ac0 + ((x >> 1) << uvs);                               // chroma nearest neighbour
+      const vpcc_color3 c = yuv10_to_rgb8_fast(gl(ay0)[(Index)y * as0 + x] >> ash, gl(au0)[cidx] >> ash, gl(av0)[cidx] >> ash);
       col[j][0] = (uint32_t)c.r | ((uint32_t)c.g << 8) | ((uint32_t)c.b << 16);
     }
     if (has_attr && np == 2u) {
-      const uint32_t cidx = (y >> 1) * ac1 + ((x >> 1) << uvs);
-      const vpcc_color3 c = yuv10_to_rgb8_fast(gl(ay1)[y * as1 + x] >> ash, gl(au1)[cidx] >> ash, gl(av1)[cidx] >> ash);
+      const Index cidx = (Index)(y >> 1) * ac1 + ((x >> 1) << uvs);
+      const vpcc_color3 c = yuv10_to_rgb8_fast(gl(ay1)[(Index)y * as1 + x] >> ash, gl(au1)[cidx] >> ash, gl(av1)[cidx] >> ash);
       col[j][1] = (uint32_t)c.r | ((uint32_t)c.g << 8) | ((uint32_t)c.b << 16);
     }
   }
@@ -938,7 +941,7 @@ __global__ __launch_bounds__(256) void k_upsample_occupancy(const DevFrame* __re
                                                             uint8_t* __restrict__ out) {
   const DevFrame& f = frames[frame];
   const uint32_t x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (x < f.width) out[(size_t)y * f.width + x] = gl(f.occ)[(y / f.prec) * f.occ_stride + (x / f.prec)];
+  if (x < f.width) out[(size_t)y * f.width + x] = gl(f.occ)[(size_t)(y / f.prec) * f.occ_stride + (x / f.prec)];
 }
 
 // ----------------------------------------------------------------- launchers
@@ -949,24 +952,32 @@ void launch_block_owner(const DevFrame* d_frames, uint32_t first, uint32_t count
   else
     hipLaunchKernelGGL(k_block_owner<64>, dim3((max_vb + 3) / 4, count), dim3(256), 0, (hipStream_t)stream, d_frames, first);
 }
-void launch_general(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_units, uint32_t gen, bool block_units,
-                    bool layout, void* stream) {
-  if (!count || !max_units) return;
+bool launch_general(const DevFrame* d_frames, uint32_t first, uint32_t count, uint32_t max_units, uint32_t gen, bool block_units,
+                    bool layout, bool wide, void* stream) {
+  if (!count || !max_units) return true;
+  constexpr uint64_t kMaxGroups = 0xFFFFFFFFull / kGenThreads;              // a grid's threads: below 2^32
   if (block_units) {
     const uint32_t groups = (max_units + kGenBlockUnits - 1u) / kGenBlockUnits;
     const GenShape shape = gen_shape(count, groups, kGenInterleave);
+    if (shape.grid > kMaxGroups) return false;
     if (layout)
       hipLaunchKernelGGL((k_general_blocks<true>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
     else
       hipLaunchKernelGGL((k_general_blocks<false>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
-    return;
+    return true;
   }
   const uint32_t groups = (max_units + kGenUnitsPerGroup - 1u) / kGenUnitsPerGroup;
   const GenShape shape = gen_shape(count, groups, kGenInterleave);
-  if (layout)
+  if (shape.grid > kMaxGroups) return false;
+  if (wide && layout)
+    hipLaunchKernelGGL((k_general<true, true>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
+  else if (wide)
+    hipLaunchKernelGGL((k_general<false, true>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
+  else if (layout)
     hipLaunchKernelGGL((k_general<true>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
   else
     hipLaunchKernelGGL((k_general<false>), dim3(shape.grid), dim3(kGenThreads), 0, (hipStream_t)stream, d_frames, first, count, groups, shape.interleave, shape.lanes, gen);
+  return true;
 }
 // Plane ingest by the GPU itself: every workgroup pulls 64-KB pieces of page-locked HOST memory over PCIe (zero-copy
 // reads, 16 B per lane, coalesced) and stores them in HBM.  One launch moves all planes of a gof: 57 GB/s with 64
