@@ -452,6 +452,61 @@ int vpcc_gof_output_digests(vpcc_gof* gof, uint32_t first, uint32_t count, uint6
  * are when the kernel runs (behind the gof's ingest and launches); waits for the result. */
 int vpcc_gof_plane_digests(vpcc_gof* gof, uint32_t first, uint32_t count, uint64_t* out /* count */);
 
+/* ---------------------------------------------------------------- cloud metrics */
+/* Point-to-point geometry error and colour error between two point clouds, computed on the GPU (vpcc_metrics.hip).  This is
+ * the library's OWN specification, in the spirit of MPEG's pc_error; it does not reproduce pc_error's duplicate-point
+ * handling (dropdups) nor its averaging over tied neighbours (neighborsProc).
+ *
+ * Nearest neighbour of a source point s in a target cloud T: the point t of T with the smallest
+ *   d²(s, t) = (s.x − t.x)² + (s.y − t.y)² + (s.z − t.z)²,
+ * exact in integers, over the whole uint16 range.  Ties go to the SMALLEST index in T: the result does not depend on the
+ * order of the search.
+ * One direction S→T sums over the points s of S, nn(s) its nearest neighbour:
+ *   geo_sse    = Σ d²(s, nn(s)) (exact uint64),  geo_max = max d²(s, nn(s)) (3 · 65535² does not fit 32 bits)
+ *   rgb_sse[c] = Σ (c_s − c_nn)² per channel R, G, B (exact uint64)                         — when both clouds have colours
+ *   ycc_sse[c] = Σ dY², Σ dCb², Σ dCr² (double), from dR, dG, dB = the differences c_s − c_nn as doubles:
+ *       dY = 0.2126·dR + 0.7152·dG + 0.0722·dB,  dCb = −0.1146·dR − 0.3854·dG + 0.5·dB,  dCr = 0.5·dR − 0.4542·dG − 0.0458·dB
+ *     each evaluated left to right without fused multiply-adds, then squared; the sums are reduced in a fixed order, so two
+ *     runs give bit-identical doubles.
+ * An empty target gives no terms (n_tgt = 0 tells the caller; not an error: a frame can empty).  A source of more than
+ * 1 431 655 765 points, whose geo_sse could overflow, is refused with VPCC_ERR_UNSUPPORTED, as is a pair of more than 2^31
+ * points in all.  The figures derived from both directions A→B and B→A (D1 MSE = max(sse_ab / n_a, sse_ba / n_b),
+ * D1 PSNR = 10·log10(3·peak² / D1 MSE), Hausdorff² = max of both geo_max, per colour channel MSE = max of both directions and
+ * PSNR = 10·log10(255² / MSE)) are the caller's (tmc2rs.recon.psnr).
+ *
+ * Memory: VPCC_MEM_HOST clouds (and host outputs) are staged by the call, through a page-locked buffer the context keeps: the
+ * caller's memory is only read and written by the CPU.  VPCC_MEM_DEVICE clouds are borrowed and must be complete when
+ * the call is made (it is ordered on the context's stream only).  Every call waits for its result. */
+typedef struct vpcc_cloud {
+  const vpcc_point3* xyz;          /* n positions */
+  const vpcc_color3* rgb;          /* n colours, or NULL: no colour terms */
+  uint32_t n;
+  uint32_t reserved;               /* 0 */
+} vpcc_cloud;
+typedef struct vpcc_cloud_errors {
+  uint32_t n_src, n_tgt;           /* points of the source and of the target of this direction */
+  uint32_t has_color;              /* both clouds have colours: rgb_sse / ycc_sse hold sums (else 0) */
+  uint32_t reserved;
+  uint64_t geo_sse, geo_max;
+  uint64_t rgb_sse[3];
+  double ycc_sse[3];
+} vpcc_cloud_errors;
+/* Both directions of n_pairs pairs (a[i], b[i]) in one call: ab_out[i] = a[i]→b[i], ba_out[i] = b[i]→a[i].  The pairs are
+ * processed in chunks whose scratch fits a limit (4 GiB). */
+int vpcc_cloud_errors_compute(vpcc_ctx* ctx, const vpcc_cloud* a, const vpcc_cloud* b, uint32_t n_pairs, vpcc_memory_kind mem,
+                              vpcc_cloud_errors* ab_out, vpcc_cloud_errors* ba_out);
+/* The correspondence of one direction s→t, point by point: index_out[i] = the index in t of source point i's nearest
+ * neighbour, dist2_out[i] = its d² (either may be NULL), in memory of the kind `mem` (s->n entries each).  With an empty
+ * target every entry is 0xFFFFFFFF / UINT64_MAX.  The building block of point-to-plane errors and error maps. */
+int vpcc_cloud_nearest(vpcc_ctx* ctx, const vpcc_cloud* s, const vpcc_cloud* t, vpcc_memory_kind mem, uint32_t* index_out,
+                       uint64_t* dist2_out);
+/* Both directions between frames [first, first+count) of the gof (side A: its device outputs, with colours when the frame
+ * has attributes) and refs[0 .. count) (side B, in memory of the kind `mem`): stream-ordered behind everything enqueued on
+ * the gof (reconstruct, smooth), as vpcc_gof_output_digests is.  VPCC_ERR_STATE before the first launch; VPCC_ERR_CAPACITY
+ * for a frame whose last launch overflowed the gof's capacity. */
+int vpcc_gof_cloud_errors(vpcc_gof* gof, uint32_t first, uint32_t count, const vpcc_cloud* refs, vpcc_memory_kind mem,
+                          vpcc_cloud_errors* ab_out, vpcc_cloud_errors* ba_out);
+
 /* ------------------------------------------------- host mirror of the library API */
 /* C view of the C++ class tmc2rs::Decoder (tmc2-rs_amd/csrc/decoder.hpp), which mirrors the
  * reference's public API: Decoder::new (src/lib.rs:71-78), start() (:97-138), recv_frame() (:143-145).

@@ -63,6 +63,8 @@ extern "C" void vpcc_ctx_destroy(vpcc_ctx* ctx) {
   for (auto& a : ctx->arena_cache) (void)hipFree(a.first);
   for (auto& a : ctx->stage_cache) (void)hipHostFree(a.first);
   for (auto& b : ctx->digest_cache) { (void)hipFree(b.dev); (void)hipHostFree(b.host); }
+  if (ctx->metrics_scratch) (void)hipFree(ctx->metrics_scratch);
+  if (ctx->metrics_host) (void)hipHostFree(ctx->metrics_host);
   for (auto& b : ctx->lent) release_block(ctx, b);          // (what a producer still holds goes with the context)
   ctx->lent.clear();
   retire_pool(ctx);

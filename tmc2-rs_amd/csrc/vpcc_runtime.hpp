@@ -56,6 +56,12 @@ struct vpcc_ctx {
   // Frame digests (vpcc_digest.hip): a gof's slots on the device and their page-locked copy, kept for the next gof that asks
   struct DigestBuffers { void* dev = nullptr; void* host = nullptr; size_t bytes = 0; };
   std::vector<DigestBuffers> digest_cache;
+  // Cloud metrics (vpcc_metrics.hip): one scratch allocation and one page-locked staging buffer, grown on demand and kept
+  // until the context goes
+  void* metrics_scratch = nullptr;
+  size_t metrics_bytes = 0;
+  void* metrics_host = nullptr;
+  size_t metrics_host_bytes = 0;
 };
 
 struct KernelTiming {

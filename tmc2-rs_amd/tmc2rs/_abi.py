@@ -225,6 +225,15 @@ class VerifyStats(C.Structure):
                 ("kernel_seconds", C.c_double)]
 
 
+class Cloud(C.Structure):               # vpcc_cloud
+    _fields_ = [("xyz", C.c_void_p), ("rgb", C.c_void_p), ("n", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CloudErrors(C.Structure):         # vpcc_cloud_errors
+    _fields_ = [("n_src", C.c_uint32), ("n_tgt", C.c_uint32), ("has_color", C.c_uint32), ("reserved", C.c_uint32),
+                ("geo_sse", C.c_uint64), ("geo_max", C.c_uint64), ("rgb_sse", C.c_uint64 * 3), ("ycc_sse", C.c_double * 3)]
+
+
 def load_library():
     """Loads libvpcc_recon.so (built in-tree by `make` / __graft_entry__.build()).
     Raises — never falls back — when it is missing."""
@@ -298,6 +307,10 @@ def load_library():
     lib.vpcc_digest_frame_planes.argtypes = [FD, C.POINTER(u64)]
     lib.vpcc_gof_output_digests.argtypes = [vp, u32, u32, vp]
     lib.vpcc_gof_plane_digests.argtypes = [vp, u32, u32, vp]
+    CL, CE = C.POINTER(Cloud), C.POINTER(CloudErrors)
+    lib.vpcc_cloud_errors_compute.argtypes = [vp, CL, CL, u32, C.c_int, CE, CE]
+    lib.vpcc_cloud_nearest.argtypes = [vp, CL, CL, C.c_int, vp, vp]
+    lib.vpcc_gof_cloud_errors.argtypes = [vp, u32, u32, CL, C.c_int, CE, CE]
     lib.vpcc_decoder_set_verify.argtypes = [vp, u32]
     lib.vpcc_decoder_set_video_format.argtypes = [vp, C.c_int]
     lib.vpcc_decoder_frame_digest.argtypes = [vp, C.POINTER(u64)]

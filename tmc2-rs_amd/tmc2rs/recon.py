@@ -58,6 +58,113 @@ def digest_planes(frame):
     return out.value
 
 
+# ---------------------------------------------------------------- cloud metrics (include/vpcc_recon.h, "cloud metrics")
+def _errors_dict(e):
+    return {"n_src": int(e.n_src), "n_tgt": int(e.n_tgt), "has_color": bool(e.has_color), "geo_sse": int(e.geo_sse),
+            "geo_max": int(e.geo_max), "rgb_sse": [int(v) for v in e.rgb_sse], "ycc_sse": [float(v) for v in e.ycc_sse]}
+
+
+def _term(sse, d):
+    """sse / n_src of one direction; NaN where it has no terms (an empty source or target)."""
+    return float(sse) / d["n_src"] if d["n_src"] and d["n_tgt"] else float("nan")
+
+
+def _nanmax(x, y):
+    return float("nan") if x != x or y != y else max(x, y)
+
+
+def _psnr(num, mse):
+    if mse != mse:
+        return float("nan")
+    return float("inf") if mse == 0 else 10.0 * float(np.log10(num / mse))
+
+
+def psnr(ab, ba, peak):
+    """The derived figures of the two directions ab = A->B and ba = B->A (dicts of Context.cloud_errors):
+    D1 MSE = max(sse_ab / n_a, sse_ba / n_b), D1 PSNR = 10 log10(3 peak^2 / D1 MSE), Hausdorff^2 = max of both geo_max, and per
+    colour channel (R, G, B and Y, Cb, Cr) MSE = max of both directions, PSNR = 10 log10(255^2 / MSE).  PSNR is +inf at MSE 0
+    and NaN where a direction has no terms (colour: where either direction has no colours)."""
+    d1 = _nanmax(_term(ab["geo_sse"], ab), _term(ba["geo_sse"], ba))
+    out = {"d1_mse": d1, "d1_psnr": _psnr(3.0 * float(peak) ** 2, d1), "hausdorff2": max(int(ab["geo_max"]), int(ba["geo_max"]))}
+    colour = ab["has_color"] and ba["has_color"]
+    for key in ("rgb", "ycc"):
+        mse = [_nanmax(_term(ab[key + "_sse"][c], ab), _term(ba[key + "_sse"][c], ba)) if colour else float("nan")
+               for c in range(3)]
+        out[key + "_mse"] = mse
+        out[key + "_psnr"] = [_psnr(255.0 ** 2, m) for m in mse]
+    return out
+
+
+def _is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def _cloud(c):
+    """(vpcc_cloud, memory kind, keepalive) of a cloud: an (n, 3) xyz array, a pair (xyz, rgb) or a dict {"xyz", "rgb"};
+    rgb (n, 3) or None.  numpy arrays are host clouds (VPCC_MEM_HOST); CUDA torch tensors (xyz of 2-byte, rgb of 1-byte
+    elements, contiguous) are device clouds (VPCC_MEM_DEVICE)."""
+    if isinstance(c, dict):
+        xyz, rgb = c["xyz"], c.get("rgb")
+    elif isinstance(c, (tuple, list)):
+        xyz, rgb = c
+    else:
+        xyz, rgb = c, None
+    cl = _abi.Cloud()
+    if _is_torch(xyz):
+        if not xyz.is_cuda or xyz.element_size() != 2 or not xyz.is_contiguous() or xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError("a device cloud's xyz is a contiguous (n, 3) CUDA tensor of 2-byte elements")
+        n = xyz.shape[0]
+        if rgb is not None and (not _is_torch(rgb) or not rgb.is_cuda or rgb.element_size() != 1 or not rgb.is_contiguous()
+                                or tuple(rgb.shape) != (n, 3)):
+            raise ValueError("a device cloud's rgb is a contiguous (n, 3) CUDA tensor of bytes")
+        cl.xyz = xyz.data_ptr() if n else None
+        cl.rgb = rgb.data_ptr() if rgb is not None and n else None
+        if rgb is not None and not n:
+            cl.rgb = xyz.data_ptr() or 1                    # (an empty cloud with colours: any non-null pointer)
+        cl.n = n
+        return cl, VPCC_MEM_DEVICE, (xyz, rgb)
+    xyz = np.ascontiguousarray(xyz, dtype=np.uint16).reshape(-1, 3)
+    n = xyz.shape[0]
+    keep = [xyz]
+    cl.xyz = xyz.ctypes.data if n else None
+    if rgb is not None:
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
+        if rgb.shape[0] != n:
+            raise ValueError("xyz and rgb differ in length")
+        keep.append(rgb)
+        cl.rgb = rgb.ctypes.data
+    cl.n = n
+    return cl, VPCC_MEM_HOST, keep
+
+
+def _clouds(clouds):
+    arr = (_abi.Cloud * max(len(clouds), 1))()
+    kinds, keep = set(), []
+    for i, c in enumerate(clouds):
+        arr[i], kind, k = _cloud(c)
+        kinds.add(kind)
+        keep.append(k)
+    if len(kinds) > 1:
+        raise ValueError("host and device clouds in one call")
+    return arr, (kinds.pop() if kinds else VPCC_MEM_HOST), keep
+
+
+def _sync_if_device(kind):
+    if kind == VPCC_MEM_DEVICE:                   # the clouds are read on the context's stream: torch's work on them first
+        import torch
+        torch.cuda.synchronize()
+
+
+def _pairs_result(ab, ba, n, peak):
+    res = []
+    for i in range(n):
+        r = {"ab": _errors_dict(ab[i]), "ba": _errors_dict(ba[i])}
+        if peak is not None:
+            r.update(psnr(r["ab"], r["ba"], peak))
+        res.append(r)
+    return res
+
+
 def _root(a):
     """The numpy buffer that owns a plane's memory (a strided view's base)."""
     while isinstance(a.base, np.ndarray):
@@ -237,6 +344,47 @@ class Context:
             res["patch_index"] = pidx[:k].copy()
         return res
 
+    def cloud_errors(self, a, b, peak=None):
+        """vpcc_cloud_errors_compute: both directions between cloud a and cloud b, or between a[i] and b[i] for two lists.
+        A cloud: an (n, 3) xyz array, (xyz, rgb) or {"xyz", "rgb"}; numpy arrays or CUDA torch tensors (all of one kind).
+        Returns {"ab": {...}, "ba": {...}} per pair, with the figures of psnr() when `peak` is given (1023 for 10-bit)."""
+        single = not isinstance(a, list)
+        a, b = ([a], [b]) if single else (a, b)
+        if len(a) != len(b):
+            raise ValueError("a and b differ in length")
+        ca, ka, keep_a = _clouds(a)
+        cb, kb, keep_b = _clouds(b)
+        if a and ka != kb:
+            raise ValueError("host and device clouds in one call")
+        n = len(a)
+        ab, ba = (_abi.CloudErrors * max(n, 1))(), (_abi.CloudErrors * max(n, 1))()
+        _sync_if_device(ka)
+        self._check(self.lib.vpcc_cloud_errors_compute(self.h, ca, cb, n, ka, ab, ba), "vpcc_cloud_errors_compute")
+        res = _pairs_result(ab, ba, n, peak)
+        return res[0] if single else res
+
+    def cloud_nearest(self, s, t):
+        """vpcc_cloud_nearest: (index, dist2) of every point of s in t — uint32 / uint64 numpy arrays for host clouds, int64
+        CUDA tensors for device clouds (index 0xFFFFFFFF and dist2 2^64 - 1, resp. -1, where t is empty)."""
+        cs, ks, keep_s = _cloud(s)
+        ct, kt, keep_t = _cloud(t)
+        if ks != kt:
+            raise ValueError("host and device clouds in one call")
+        n = int(cs.n)
+        if ks == VPCC_MEM_DEVICE:
+            import torch
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=keep_s[0].device)
+            d2 = torch.empty(max(n, 1), dtype=torch.int64, device=keep_s[0].device)
+            _sync_if_device(ks)
+            self._check(self.lib.vpcc_cloud_nearest(self.h, C.byref(cs), C.byref(ct), ks, idx.data_ptr(), d2.data_ptr()),
+                        "vpcc_cloud_nearest")
+            return idx[:n].to(torch.int64) & 0xFFFFFFFF, d2[:n]
+        idx = np.zeros(max(n, 1), np.uint32)
+        d2 = np.zeros(max(n, 1), np.uint64)
+        self._check(self.lib.vpcc_cloud_nearest(self.h, C.byref(cs), C.byref(ct), ks, idx.ctypes.data, d2.ctypes.data),
+                    "vpcc_cloud_nearest")
+        return idx[:n], d2[:n]
+
     def gof(self, frames, capacity=0, flags=0, memory=VPCC_MEM_HOST, descs=None):
         return Gof(self, frames, capacity, flags, memory, descs)
 
@@ -371,6 +519,18 @@ class Gof:
     def plane_digests(self, first=0, count=None):
         """vpcc_gof_plane_digests: the plane digest of every frame of [first, first+count) over its device planes."""
         return self._digests(self.lib.vpcc_gof_plane_digests, first, count, "vpcc_gof_plane_digests")
+
+    def cloud_errors(self, refs, first=0, count=None, peak=None):
+        """vpcc_gof_cloud_errors: both directions between frames [first, first+count) of the gof as they are on the device
+        (side A) and the clouds `refs` (side B, one per frame; see Context.cloud_errors), behind the gof's launches."""
+        count = self.n_frames - first if count is None else count
+        if len(refs) != count:
+            raise ValueError("one reference cloud per frame")
+        cr, kind, keep = _clouds(refs)
+        ab, ba = (_abi.CloudErrors * max(count, 1))(), (_abi.CloudErrors * max(count, 1))()
+        _sync_if_device(kind)
+        self.ctx._check(self.lib.vpcc_gof_cloud_errors(self.h, first, count, cr, kind, ab, ba), "vpcc_gof_cloud_errors")
+        return _pairs_result(ab, ba, count, peak)
 
     def algorithmic_bytes(self, frame):
         b = C.c_uint64(0)
